@@ -2,6 +2,21 @@
 """bench.py — frames/s and Mrays/s of the MI355X ray tracer (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--mode auto|frames|strong|weak]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up (W steps per frame in flight), times K steps and
+prints the JSON line: value, ms_per_step, fps and what describes the run. The timed
+steps follow the warm-up directly: a run of a few dozen steps after a short warm-up
+times a device that has been busy for a few milliseconds only (30 steps after
+--warmup 3: 0.190 ms per car frame, against 0.179 ms with --full, whose earlier
+passes keep the device busy first, or with 300 steps either way). --full
+adds everything else described below (the one-at-a-time and waited-frame passes,
+the device-time pass and the roofline, the CPU baselines, the parity checks); their
+fields are null in a plain line. --dump-outputs DIR writes the image the last timed
+step produced (what a caller of the timed path receives) as DIR/image.npy, float32
+[H, W, 4]; the inputs are the same from run to run, so two builds can be compared
+pixel for pixel. A 3840x2160 image is over 64 MB: a fixed seeded sample of its
+pixels is written instead, with their flat indices in DIR/image_pixels.npy.
 
 A step is one frame of the reference's GPU render loop (src/main.cpp:325-370):
 the per-frame camera + light upload (SSBO 2/1), the render dispatch and its
@@ -23,8 +38,8 @@ Modes (--mode auto = frames at N = 1, strong at N > 1):
           over xGMI, then k_unstripe into rank 0's image) — total work fixed,
           scaling "strong". Frames in flight = the group's frame slots
           (rt_group_set_frames): one render stream and buffer set per slot,
-          ONE communicator and one fan-in stream per rank. Before timing,
-          one gathered frame is compared bit for bit with rank 0's own
+          ONE communicator and one fan-in stream per rank. With --full,
+          before timing, one gathered frame is compared bit for bit with rank 0's own
           single-GPU frame (exit 5 on a mismatch); every wait on the group
           is bounded (rt_group_sync: exit 4 on a timeout or an RCCL error);
           the JSON line carries each rank's render / fan-in / unstripe times.
@@ -35,7 +50,7 @@ Modes (--mode auto = frames at N = 1, strong at N > 1):
 
 value = Mrays/s = (closest-hit + shadow rays of the frame, counted on the
 reference walk by the counting kernel) x frames / s, summed over the job.
-Rank 0 prints one JSON line with the render kernel's roofline and the CPU
+Rank 0 prints one JSON line, with --full with the render kernel's roofline and the CPU
 baseline (N = 1 only: the oracle, OpenMP on the host's cores, on a bounded row
 sample of the same frame; plus the reference's 1-core cpuRayTracer).
 
@@ -126,6 +141,14 @@ def parse(argv=None):
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the host's cores (nproc)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearse the N>1 path with every rank on one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the one-at-a-time and waited-frame passes, the device-time "
+                         "pass and the roofline, the CPU baselines, the oracle parity check of the timed frames "
+                         "and (strong mode over rt_group) the bit-exact check against the single-GPU frame")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes the image its last timed step produced as "
+                         "DIR/image.npy (float32 [H, W, 4]; above 64 MB a fixed seeded sample of its pixels, "
+                         "with their flat indices in DIR/image_pixels.npy)")
     return ap.parse_args(argv)
 
 
@@ -219,6 +242,26 @@ def parity_check(frames, ref_y0, ref, what):
         bad += int((d > PARITY_TOL).any(axis=-1).sum())
     return {"max_abs": worst, "bad_pixels": bad, "frames_checked": len(frames), "tol": PARITY_TOL,
             "rows_checked": [int(ref_y0), int(ref_y0 + len(ref))], "against": what, "ok": bad == 0}
+
+
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write
+
+
+def dump_outputs(path, image):
+    """--dump-outputs: the image of the last timed step as path/image.npy (float32).
+    An image over DUMP_LIMIT (3840x2160) is written as a sample instead: the pixels
+    drawn by a fixed seed, in index order, and their flat indices (y * W + x, exact
+    in float64) as path/image_pixels.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.nbytes > DUMP_LIMIT:
+        px = img.reshape(-1, img.shape[-1])
+        n = DUMP_LIMIT // 32  # 16 B per pixel and 8 B per index: 3/4 of the limit
+        idx = np.sort(np.random.default_rng(0).choice(len(px), n, replace=False))
+        np.save(os.path.join(path, "image_pixels.npy"), idx.astype(np.float64))
+        img = px[idx]
+    np.save(os.path.join(path, "image.npy"), img)
 
 
 def cpu_reference_1core(rtamd, seconds, cfg=3, variant=0, W=1920, H=1080):
@@ -594,7 +637,9 @@ def main():
         buf = bufs[i % inflight]
         c_.dispatch_rows(W, H, plan.y0(prank), a.stripe, plan.world, rows, buf.data_ptr(), W * 16)
         if strong:
-            tiling.gather_to_root(buf, plan)
+            gathered[0] = tiling.gather_to_root(buf, plan)
+
+    gathered = [None]  # the torch path's last assembled frame (rank 0; --dump-outputs)
 
     def group_sync():
         """rt_group_sync is bounded: a fan-in that never completes or an RCCL error
@@ -646,10 +691,10 @@ def main():
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         return float(el[0])
 
-    # Strong mode over rt_group: before anything is timed, one gathered frame per frame
-    # slot is compared bit for bit with rank 0's own single-GPU frame of the same camera.
+    # Strong mode over rt_group with --full: before anything is timed, one gathered frame per
+    # frame slot is compared bit for bit with rank 0's own single-GPU frame of the same camera.
     phases, selfcheck = {}, None
-    if use_group:
+    if use_group and a.full:
         verdict = torch.zeros(1, dtype=torch.int64, device="cpu" if gloo else dev)
         want = None
         solo = None
@@ -706,8 +751,11 @@ def main():
         share_probe = {str(k): v for k, v in share_probe.items()}
         rays_step, b_ref_rank, rows = count_work()  # this rank's rows at the chosen share
 
-    serial = timed(1) if F > 1 else None  # device times recorded: the roofline's kernel time
-    serial_kt = ctx.kernel_times() if F > 1 else None
+    # Everything between here and the timed steps, and after them the device-time pass, the
+    # roofline, the CPU baselines and the parity checks, runs with --full only: a plain run
+    # sets up, warms up, times a.steps steps and prints the line.
+    serial = timed(1) if a.full and F > 1 else None  # device times recorded: the roofline's kernel time
+    serial_kt = ctx.kernel_times() if a.full and F > 1 else None
     set_timing(F == 1)  # F = 1 (the profilers' --inflight 1): the main pass is the device-time pass
     # SURVEY §8(d)'s frame: upload + dispatch + completion, one at a time, FPS = 1 / median.
     # Each frame waits for its completion (the reference's loop, src/main.cpp:290-462), with
@@ -723,7 +771,7 @@ def main():
     # where 48 frames would take over 0.1 s (config 5: 30; the brute-force 100k frames: none)
     est_ms = serial / a.steps * 1e3 if serial else None
     wait_warmup = max(a.warmup, 48 if est_ms is None else min(48, int(100.0 / max(est_ms, 1e-3))))
-    if not (strong and not use_group):  # the torch-gather rehearsal has no waited-frame figure
+    if a.full and not (strong and not use_group):  # the torch-gather rehearsal has no waited-frame figure
         for c_ in ctxs:
             c_.set_latency_mode(1)
 
@@ -755,7 +803,7 @@ def main():
     # Python loop's figure above is kept beside it.
     serial_frames_py = serial_frames
     serial_frames_host = []
-    if grp is None and not strong:
+    if a.full and grp is None and not strong:
         for c_ in ctxs:
             c_.set_latency_mode(1)
         frames_anim = anim[1] if anim is not None else None
@@ -777,13 +825,22 @@ def main():
     # the same one-at-a-time frames with rt_set_latency_mode (what a host that waits for
     # each frame would set); reported beside serial_ms_per_step, not used for the roofline
     serial_lat = None
-    if F > 1 and not use_group:
+    if a.full and F > 1 and not use_group:
         ctx.set_latency_mode(1)
         serial_lat = timed(1)
         ctx.set_latency_mode(0)
         ctx.kernel_times()
     elapsed = timed(F)
-    if F > 1:
+    if a.dump_outputs and rank == 0:
+        # the frame of step a.steps - 1, before any later pass renders into the same buffers
+        if use_group:
+            last_image = grp.read_image(W, H)
+        elif strong:
+            last_image = gathered[0].cpu().numpy()
+        else:
+            last_image = bufs[(a.steps - 1) % F][:rows].cpu().numpy()
+        dump_outputs(a.dump_outputs, last_image)
+    if a.full and F > 1:
         # the same frames in flight again with the device-time events, for the phase
         # times and kernel_ms_mean_inflight only (not timed)
         set_timing(True)
@@ -804,11 +861,12 @@ def main():
     # The render kernel's duration is taken where it runs alone (the one-frame-in-flight
     # pass): with frames in flight a dispatch's events also span the time it waits for
     # the other frame's waves to leave the CUs.
-    kt = serial_kt if F > 1 else kt_if
+    kt = serial_kt if serial_kt is not None else kt_if
     info = ctx.accel_info()
     kname = {1: "k_lane", 2: "k_packet", 3: "k_accel"}.get(info["last_kernel"], "?")
-    k_ms = float(np.mean(kt)) if len(kt) else float("nan")
-    k_med = float(np.median(kt)) if len(kt) else float("nan")
+    no_kt = float("nan") if a.full else None  # a plain run with frames in flight records no device times
+    k_ms = float(np.mean(kt)) if len(kt) else no_kt
+    k_med = float(np.median(kt)) if len(kt) else no_kt
 
     if rank == 0:
         frames = a.steps * (world if mode == "weak" else 1)
@@ -833,9 +891,11 @@ def main():
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": elapsed / a.steps * 1e3,
+            "full": a.full,
             "frames_in_flight": F,
             "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "4 (HIP default)"),
-            "serial_ms_per_step": (serial if serial is not None else elapsed) / a.steps * 1e3,
+            "serial_ms_per_step": ((serial if serial is not None else elapsed) / a.steps * 1e3
+                                   if a.full or F == 1 else None),
             "serial_ms_per_step_latency_mode": (serial_lat / a.steps * 1e3) if serial_lat is not None else None,
             "serial_frame_ms_median": float(np.median(serial_frames)) * 1e3 if serial_frames else None,
             "serial_frame_ms_median_python": float(np.median(serial_frames_py)) * 1e3 if serial_frames_py else None,
@@ -884,15 +944,16 @@ def main():
             "rays_per_step": rays_step,
             "kernel_ms_mean": k_ms,
             "kernel_ms_median": k_med,
-            "kernel_ms_mean_inflight": float(np.mean(kt_if)) if len(kt_if) else float("nan"),
-            "roofline": roofline(info, kname, k_ms, rows * W, b_ref_rank, pmc, share=rows / H if strong else None),
+            "kernel_ms_mean_inflight": float(np.mean(kt_if)) if len(kt_if) else no_kt,
+            "roofline": (roofline(info, kname, k_ms, rows * W, b_ref_rank, pmc, share=rows / H if strong else None)
+                         if a.full else None),
             "accel": info,
             "scene_updates": refits if anim is not None else None,
             "cpu_baseline": None,
             "parity": None,
         }
         thr = a.cpu_threads or host_cores()
-        if world == 1 and not a.no_cpu:
+        if a.full and world == 1 and not a.no_cpu:
             out["cpu_baseline"] = cpu_baseline(rtamd, fs, W, H, mb, a.cpu_seconds, thr,
                                                (not a.brute, a.fresnel, a.mt))
             out["cpu_baseline"]["reference_cpu_path"] = cpu_reference_1core(rtamd, a.cpu_seconds / 2, cfg, a.variant,
@@ -901,7 +962,7 @@ def main():
         if moving:
             out["camera_path"] = {"kind": a.camera_path, "cameras": len(cams),
                                   "last_camera_per_renderer": [x for x in last_cam if x is not None]}
-        if use_group and anim is not None:
+        if a.full and use_group and anim is not None:
             # rank 0's last gathered frame against the oracle rendering the group's scene
             # (every slot context was given every frame: the last records, and the node
             # boxes grown by all of them); outside the timed region, whole frame
@@ -918,7 +979,7 @@ def main():
                                           "camera, the group's last records and node boxes grown over every frame "
                                           "it was given"),
                                  animation_frames_applied=[len(applied[0])])
-        if mode == "frames" and (anim is not None or moving):
+        if a.full and mode == "frames" and (anim is not None or moving):
             # every renderer's last timed frame against the oracle rendering that
             # renderer's scene: its last frame's camera, and when animated its last
             # records and the boxes grown by every frame it was given (outside the timed
@@ -951,7 +1012,7 @@ def main():
                              "animation_frames_applied": [len(x) for x in applied] if anim is not None else None,
                              "host_nodes_equal_oracle": host_nodes_ok if ref_up is not None else None,
                              "ok": all(c["ok"] for c in checks) and host_nodes_ok}
-        if mode == "frames" and anim is None and not moving:
+        if a.full and mode == "frames" and anim is None and not moving:
             # the timed frames themselves, against the oracle (outside the timed region)
             if out["cpu_baseline"] is not None:
                 ry0, ref = cpu_baseline.last_image

@@ -121,6 +121,29 @@ def test_parity_check_of_timed_frames():
     assert bench.parity_check([g2], 3, ref2, "t")["ok"]
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: an image within the limit is written whole as float32; a larger
+    one as the same seeded sample of its pixels every time, with their flat indices."""
+    assert bench.DUMP_LIMIT == 64 << 20
+    a = bench.parse(["--dump-outputs", "d", "--full"])
+    assert a.dump_outputs == "d" and a.full and not bench.parse([]).full and bench.parse([]).dump_outputs is None
+    img = np.random.default_rng(2).random((9, 7, 4))
+    bench.dump_outputs(str(tmp_path / "whole"), img)
+    got = np.load(tmp_path / "whole" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.astype(np.float32))
+    assert [p.name for p in (tmp_path / "whole").iterdir()] == ["image.npy"]
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 32 * 20)  # 20 of the 63 pixels
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), img)
+    idx = np.load(tmp_path / "s1" / "image_pixels.npy")
+    px = np.load(tmp_path / "s1" / "image.npy")
+    assert idx.dtype == np.float64 and px.dtype == np.float32 and px.shape == (20, 4)
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < 63
+    assert np.array_equal(px, img.astype(np.float32).reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "image_pixels.npy"))
+    assert px.nbytes + idx.nbytes <= 32 * 20
+
+
 def test_roofline_names_the_binding_resource():
     """With the SQ passes' issue floors the line says what binds: latency when the
     busiest issue pipe's floor is a larger fraction of the kernel time than HBM."""

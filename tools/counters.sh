@@ -12,7 +12,7 @@ for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ
            "TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $OUT/p$i -o run -- \
-      python3 bench.py --no-cpu "$@" > $OUT/bench_p$i.json 2> $OUT/p$i.err || { echo "pass $i failed"; tail -20 $OUT/p$i.err; exit 1; }
+      python3 bench.py --full --no-cpu "$@" > $OUT/bench_p$i.json 2> $OUT/p$i.err || { echo "pass $i failed"; tail -20 $OUT/p$i.err; exit 1; }
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

@@ -13,7 +13,7 @@ for set in "TA_BUSY_avr TA_TA_BUSY_sum GRBM_GUI_ACTIVE" \
            "TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum GRBM_COUNT"; do
   i=$((i+1))
   timeout -k 10 -s KILL 120 rocprofv3 --pmc $set --output-format csv -d $OUT/p$i -o run -- \
-      python3 bench.py --no-cpu "$@" > $OUT/bench_p$i.json 2> $OUT/p$i.err || { echo "pass $i failed"; tail -5 $OUT/p$i.err; exit 1; }
+      python3 bench.py --full --no-cpu "$@" > $OUT/bench_p$i.json 2> $OUT/p$i.err || { echo "pass $i failed"; tail -5 $OUT/p$i.err; exit 1; }
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

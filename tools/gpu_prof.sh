@@ -12,7 +12,7 @@ TAG=$1; shift
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--no-cpu --inflight 1 --steps 20 --warmup 3 $*"
+ARGS="--full --no-cpu --inflight 1 --steps 20 --warmup 3 $*"
 run() {  # name rocprof-args...
   local name=$1; shift
   timeout -k 10 240 rocprofv3 "$@" --output-format csv -d $OUT/$name -o run -- python3 bench.py $ARGS \
