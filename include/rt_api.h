@@ -237,10 +237,6 @@ int rt_last_kernel_ms(struct rt_ctx* ctx, float* ms);
  * restarts the record. Waits for those dispatches to finish. */
 int rt_kernel_times(struct rt_ctx* ctx, float* ms, int cap);
 
-/* Launch shape of the accelerated kernel: 1, 2 or 4 waves (8x8 tiles) per
- * workgroup; persistent != 0 = a resident grid pulling tiles from a counter. */
-int rt_set_launch(struct rt_ctx* ctx, int waves_per_block, int persistent);
-
 /* Accelerated kernel: bounces with depth >= lane_from_depth walk one ray per
  * lane (LDS stack) instead of one packet per wave; 0 = all bounces per lane,
  * >= maxBounces = all packet. Default (auto): 1 -- camera rays and their shadow

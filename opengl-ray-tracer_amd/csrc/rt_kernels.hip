@@ -2,24 +2,39 @@
 // include/rt_api.h (librtamd.so).
 //
 // Kernels
-//   k_pack_shapes / k_pack_nodes : AoS FlatShape/FlatNode (the reference's SSBO
-//       records) -> the HBM layout of rt_device.h (run once per upload).
+//   k_pack_shapes / k_pack_nodes / k_pack_prims : AoS FlatShape/FlatNode (the
+//       reference's SSBO records) -> the HBM layouts of rt_device.h and of the
+//       accelerator (run once per upload).
 //   k_lane<STATS>   : one ray per lane walking the reference's own traversal
 //       (stack in LDS, right child first, closest-hit shadow rays). It is the
 //       literal restatement of gpu_shader.comp and, with STATS, counts the work
 //       that shader performs (node loads, primitive tests, material fetches).
-//   k_packet        : the production kernel. A wave64 renders an 8x8 pixel tile
-//       as one packet: the tree walk order of gpu_shader.comp:384-426 does not
-//       depend on the ray, so the wave walks it once with a 64-bit active mask
+//   k_packet        : a wave64 renders an 8x8 pixel tile as one packet over the
+//       reference tree alone: the tree walk order of gpu_shader.comp:384-426 does
+//       not depend on the ray, so the wave walks it once with a 64-bit active mask
 //       per stack entry (the stack lives in the wave's VGPR lanes: entry j in
 //       lane j, readlane/writelane), node and shape records are wave-uniform
 //       scalar loads, and each lane keeps exactly the state, order and
 //       tie-breaking of its own reference walk. Shadow rays stop per lane at the
 //       first occluder closer than the light (equivalent to the reference's
-//       closest-hit test).
+//       closest-hit test). It renders the frames the accelerator
+//       cannot (accel_usable).
+//   k_accel<TIMED, COST, TAIL, MT, REC, QUEUE> : the production kernel. One 8x8
+//       tile (or one band of a split heavy tile) per wave over the exact-result
+//       accelerator (accel.h): packet walks (packet_walk) for coherent rays,
+//       per-lane walks with LDS stacks (lane_walk) for the rest, same image as
+//       the kernels above. launch() picks the instance; the one without counters,
+//       queue or records (k_accel<false, false>) renders the plain frames.
+//   k_accel_tail    : the remaining bounces of the rays k_accel queued
+//       (rt_set_tail), 64 rays from one screen region to a wave.
+//   k_tile_order / k_cost_dilate : the next frame's dispatch order from the tile
+//       costs a k_accel dispatch recorded (rt_set_schedule).
+//   k_refit / k_inf_slots : boxes and cones of moved shapes (rt_animate,
+//       rt_update_shapes / rt_update_nodes).
 //
-// Launch geometry: 256-thread blocks = 4 waves side by side = 32 x 8 pixels;
-// grid = ceil(W/32) x ceil(rows/8). Every kernel is compiled with
+// Launch geometry: k_lane and k_packet run 256-thread blocks = 4 waves side by
+// side = 32 x 8 pixels, grid = ceil(W/32) x ceil(rows/8); k_accel and
+// k_accel_tail run one wave per block. Every kernel is compiled with
 // -ffp-contract=off (Makefile) so its float sequence is the oracle's.
 #include <hip/hip_runtime.h>
 
@@ -905,9 +920,6 @@ constexpr int kWideRec = 8, kWideRecMt = 17;
 #define RT_MT_UNROLL 4  // MT wide_kids: children per unrolled step (r03j: 1 -> 4 car MT -15 %)
 #endif
 constexpr int kMtUnroll = RT_MT_UNROLL;
-#ifndef RT_MT_ILF
-#define RT_MT_ILF 1  // MT entry parameter scaled by mt_pad's 1/lf bound, not a reciprocal (car MT -2.0 %, r04zz9)
-#endif
 
 // Float `comp` of child `sl`'s box (0-2 lo.xyz, 3-5 hi.xyz) in wide record w:
 // row comp, lane sl of the SoA records; float comp of the child's 16-float
@@ -954,11 +966,9 @@ __device__ __forceinline__ Kids4 wide_kids(const AccelPtrs& A, unsigned uc, cons
                                    tl * lf, tn, tf);
                 if (hh && c.ix != 0.0f && m[5] < 3e38f)
                     hh = rta::mt_slab(c.mox, c.moy, c.moz, c.on, c, k, m, q2, pt, tn, tf);
-#if RT_MT_ILF
-                tt = tn * ilf;  // the stack's prune compares with tl, not tl * lf (ilf <= 1 / lf)
-#else
-                tt = tn * rta::rcp(lf) * 0.99999f;  // the stack's prune compares with tl, not tl * lf
-#endif
+                // the stack's prune compares with tl, not tl * lf: scaled by mt_pad's bound
+                // ilf <= 1 / lf, not by a reciprocal (car MT -2.0 %, r04zz9)
+                tt = tn * ilf;
             }
             // select-written (a lane-varying index would put t / h in scratch)
             t[0] = s2 == 0 ? tt : t[0], t[1] = s2 == 1 ? tt : t[1], t[2] = s2 == 2 ? tt : t[2];
@@ -1058,17 +1068,6 @@ __device__ __forceinline__ unsigned short f_bf16_down(float t) {
 }
 __device__ __forceinline__ float bf16_f(unsigned short b) { return __uint_as_float(static_cast<unsigned>(b) << 16); }
 
-#ifndef RT_SPLIT_ALL
-#define RT_SPLIT_ALL 0  // split walks (lane_walk_any) in every k_accel instance (experiment builds)
-#endif
-#ifndef RT_LEAF_PREFETCH
-#define RT_LEAF_PREFETCH 0  // lane_walk's leaf loop software-pipelined (experiment builds)
-#endif
-
-#ifndef RT_FLAT_LOOP
-#define RT_FLAT_LOOP 1  // lane_walk's SPEC descent as a one-exit loop (r03: config 5 -3 %)
-#endif
-
 // Per-lane walk ("while-while"): each lane walks its own stack in LDS (code +
 // entry parameter per entry). A lane descends until it holds a leaf, keeping
 // the nearer child in registers and stacking the farther one; the wave then
@@ -1089,8 +1088,7 @@ __device__ __forceinline__ float bf16_f(unsigned short b) { return __uint_as_flo
 // FLAT_SHADOW: a shadow hit sets the lane's flags and ends its leaf loop through the loop
 // test, instead of returning from inside the loop (r03: car -1.7 % in flight and serially;
 // config 5 +0.5 %, so the big-scene instances, which split walks, keep the return).
-template <bool SHADOW, bool COUNT = false, bool WSTAT = false, bool SPEC = true, bool MT = false,
-          bool FLAT_SHADOW = false>
+template <bool SHADOW, bool COUNT = false, bool WSTAT = false, bool MT = false, bool FLAT_SHADOW = false>
 __device__ void lane_walk(const AccelPtrs& A, const Ray& r, bool active, float lim_shadow, Best& b, bool& shadow,
                           int* stk, unsigned short* stt, int stride, int cap, WalkCount& wc, int sg = 1,
                           int si = 0) {
@@ -1207,151 +1205,117 @@ __device__ void lane_walk(const AccelPtrs& A, const Ray& r, bool active, float l
     if (!have) cur = kNoChild;
     bool ended = false;
     for (;;) {
-        // While-while: a lane descends until it holds a leaf. SPEC (speculative):
-        // it then keeps walking inner nodes while any other lane is still looking
-        // for one; a lane that meets a second leaf parks on it (kept for the next
-        // round), and the round ends when every walking lane holds a leaf
-        // (measured: config 3 -4 %, config 5 -14 %).
-#if RT_FLAT_LOOP
-        // SPEC in one-exit form: a lane that finishes, parks or ends its walk sets `stop`
+        // While-while, speculative: a lane descends until it holds a leaf, then keeps
+        // walking inner nodes while any other lane is still looking for one; a lane
+        // that meets a second leaf parks on it (kept for the next round), and the
+        // round ends when every walking lane holds a leaf (measured: config 3 -4 %,
+        // config 5 -14 %).
+        // One-exit form: a lane that finishes, parks or ends its walk sets `stop`
         // instead of leaving the loop, and the round ends on the wave-uniform test alone
-        // (the same steps in the same order per lane; fewer lane-mask merges per step).
+        // (fewer lane-mask merges per step; r03: config 5 -3 %). Ended lanes are
+        // stopped: no exec test around the loop (config 5: -2 %).
         bool stop = ended;
-        if (SPEC) {  // ended lanes are stopped: no exec test around the loop (config 5: -2 %)
-            for (;;) {
-                if (__ballot(!stop && count == 0) == 0) break;
-                if (!stop && cur == kNoChild) {
-                    if (sp == 0) {
-                        if (ovf) {  // a scene-tree push was dropped: the reference tree, from its root
-                            ovf = false;
-                            pcap = capo;
-                            if (!enter_root(A, r, inv, c, tl, cur)) cur = kNoChild;
-                        }
-                        if (cur == kNoChild) {
-                            ended = count == 0;  // walk finished (a held leaf is still tested)
-                            stop = true;
-                        }
-                    } else {
-                        sp -= stride;
-                        const int pc = stk[sp];
-                        cur = bf16_f(stt[sp]) > tl ? kNoChild : pc;  // dropped if a nearer hit was found since the push
+        for (;;) {
+            if (__ballot(!stop && count == 0) == 0) break;
+            if (!stop && cur == kNoChild) {
+                if (sp == 0) {
+                    if (ovf) {  // a scene-tree push was dropped: the reference tree, from its root
+                        ovf = false;
+                        pcap = capo;
+                        if (!enter_root(A, r, inv, c, tl, cur)) cur = kNoChild;
                     }
-                }
-                const unsigned uc = static_cast<unsigned>(cur);
-                stop = stop || (cur != kNoChild && count > 0 && (uc & (kTopLeaf | kLeaf)));  // park on a leaf
-                if (stop || cur == kNoChild) continue;
-#else
-        if (!ended) {
-            for (;;) {
-                if (SPEC ? __ballot(!ended && count == 0) == 0 : count > 0) break;
-                if (cur == kNoChild) {
-                    if (sp == 0) {
-                        if (ovf) {  // a scene-tree push was dropped: the reference tree, from its root
-                            ovf = false;
-                            pcap = capo;
-                            if (enter_root(A, r, inv, c, tl, cur)) continue;
-                            cur = kNoChild;
-                        }
-                        if (count == 0) ended = true;  // walk finished (a held leaf is still tested)
-                        break;
+                    if (cur == kNoChild) {
+                        ended = count == 0;  // walk finished (a held leaf is still tested)
+                        stop = true;
                     }
-                    sp -= stride;
-                    if (bf16_f(stt[sp]) > tl) continue;  // a nearer hit was found since the push
-                    cur = stk[sp];
-                }
-                const unsigned uc = static_cast<unsigned>(cur);
-                if (count > 0 && (uc & (kTopLeaf | kLeaf))) break;  // park on a leaf
-#endif
-                if (COUNT) wc.nodes++;
-                if (WSTAT && first_active()) wc.wnodes++;
-                cur = kNoChild;  // the branches below set the next node, if any
-                // kLocal codes (wide nodes and local leaves, including few-leaf items) first,
-                // as one region: a round in which no lane holds a reference-tree code skips
-                // the rest with one exec test instead of three
-                if (uc & kLocal) {
-                    if (uc & kLeaf) {
-                        start = static_cast<int>((uc >> 6) & 0x3fffffu);
-                        count = static_cast<int>(uc & 0x3fu);
-                        if (uc & kItem) count = ((fm >> (count >> 3)) & 1u) ? (count & 7) : 0;  // few-leaf item
-                    } else {
-                        auto push = [&](float t, int code) {
-                            if (t < INFINITY) {
-                                if (sp < pcap) {
-                                    stk[sp] = code;
-                                    stt[sp] = f_bf16_down(t);
-                                    sp += stride;
-                                } else {
-                                    ovf = true;  // scene tree only: local trees fit their bound
-                                }
-                            }
-                        };
-                        // a node of two records (kPair): the second record's children first,
-                        // sorted, its 2nd-4th stacked; then the first record's; the nearer of
-                        // the two records' nearest is walked, the other stacked last. One
-                        // record's values live at a time (the walk is at the VGPR cap).
-                        const bool pair = !MT && kWide8 && (uc & kPair);
-                        float vt = INFINITY;
-                        int vc = kNoChild;
-                        if (pair) {
-                            Kids4 v = wide_kids<MT>(A, uc + 1u, c, tl, true);
-                            sort4(v);
-#pragma unroll
-                            for (int s2 = 3; s2 >= 1; --s2) push(v.t[s2], v.code[s2]);
-                            vt = v.t[0];
-                            vc = v.code[0];
-                        }
-                        Kids4 w = wide_kids<MT>(A, uc, c, tl, true);
-                        sort4(w);
-#pragma unroll
-                        for (int s2 = 3; s2 >= 1; --s2) push(w.t[s2], w.code[s2]);
-                        if (pair) {
-                            const bool vf = vt < w.t[0];
-                            push(vf ? w.t[0] : vt, vf ? w.code[0] : vc);
-                            w.t[0] = vf ? vt : w.t[0];
-                            w.code[0] = vf ? vc : w.code[0];
-                        }
-                        if (w.t[0] < INFINITY) cur = w.code[0];
-                    }
-                } else if ((uc & (kTopLeaf | kItem)) == (kTopLeaf | kItem)) {
-                    int s0, n0;
-                    if (enter_item(A, uc, r, inv, s0, n0)) {
-                        start = s0;
-                        count = n0;
-                    }
-                } else if (uc & kTopLeaf) {
-                    const int4 lf = A.tleaf[uc & 0x0fffffffu];
-                    start = lf.x;
-                    count = lf.y;
-                    cur = lf.z;  // the local root (kNoChild: none) is entered with the leaf
                 } else {
-                    const Kids k = ref_kids(A, uc, r, inv, c, tl, true, fast);
-                    if (k.ha && k.hb) {
-                        const bool a_first = !(k.tb < k.ta);  // nearer entry first
-                        if (sp < capo) {
-                            stk[sp] = a_first ? k.cb : k.ca;
-                            stt[sp] = f_bf16_down(a_first ? k.tb : k.ta);
-                            sp += stride;
+                    sp -= stride;
+                    const int pc = stk[sp];
+                    cur = bf16_f(stt[sp]) > tl ? kNoChild : pc;  // dropped if a nearer hit was found since the push
+                }
+            }
+            const unsigned uc = static_cast<unsigned>(cur);
+            stop = stop || (cur != kNoChild && count > 0 && (uc & (kTopLeaf | kLeaf)));  // park on a leaf
+            if (stop || cur == kNoChild) continue;
+            if (COUNT) wc.nodes++;
+            if (WSTAT && first_active()) wc.wnodes++;
+            cur = kNoChild;  // the branches below set the next node, if any
+            // kLocal codes (wide nodes and local leaves, including few-leaf items) first,
+            // as one region: a round in which no lane holds a reference-tree code skips
+            // the rest with one exec test instead of three
+            if (uc & kLocal) {
+                if (uc & kLeaf) {
+                    start = static_cast<int>((uc >> 6) & 0x3fffffu);
+                    count = static_cast<int>(uc & 0x3fu);
+                    if (uc & kItem) count = ((fm >> (count >> 3)) & 1u) ? (count & 7) : 0;  // few-leaf item
+                } else {
+                    auto push = [&](float t, int code) {
+                        if (t < INFINITY) {
+                            if (sp < pcap) {
+                                stk[sp] = code;
+                                stt[sp] = f_bf16_down(t);
+                                sp += stride;
+                            } else {
+                                ovf = true;  // scene tree only: local trees fit their bound
+                            }
                         }
-                        cur = a_first ? k.ca : k.cb;
-                    } else if (k.ha || k.hb) {
-                        cur = k.ha ? k.ca : k.cb;
+                    };
+                    // a node of two records (kPair): the second record's children first,
+                    // sorted, its 2nd-4th stacked; then the first record's; the nearer of
+                    // the two records' nearest is walked, the other stacked last. One
+                    // record's values live at a time (the walk is at the VGPR cap).
+                    const bool pair = !MT && kWide8 && (uc & kPair);
+                    float vt = INFINITY;
+                    int vc = kNoChild;
+                    if (pair) {
+                        Kids4 v = wide_kids<MT>(A, uc + 1u, c, tl, true);
+                        sort4(v);
+#pragma unroll
+                        for (int s2 = 3; s2 >= 1; --s2) push(v.t[s2], v.code[s2]);
+                        vt = v.t[0];
+                        vc = v.code[0];
                     }
+                    Kids4 w = wide_kids<MT>(A, uc, c, tl, true);
+                    sort4(w);
+#pragma unroll
+                    for (int s2 = 3; s2 >= 1; --s2) push(w.t[s2], w.code[s2]);
+                    if (pair) {
+                        const bool vf = vt < w.t[0];
+                        push(vf ? w.t[0] : vt, vf ? w.code[0] : vc);
+                        w.t[0] = vf ? vt : w.t[0];
+                        w.code[0] = vf ? vc : w.code[0];
+                    }
+                    if (w.t[0] < INFINITY) cur = w.code[0];
+                }
+            } else if ((uc & (kTopLeaf | kItem)) == (kTopLeaf | kItem)) {
+                int s0, n0;
+                if (enter_item(A, uc, r, inv, s0, n0)) {
+                    start = s0;
+                    count = n0;
+                }
+            } else if (uc & kTopLeaf) {
+                const int4 lf = A.tleaf[uc & 0x0fffffffu];
+                start = lf.x;
+                count = lf.y;
+                cur = lf.z;  // the local root (kNoChild: none) is entered with the leaf
+            } else {
+                const Kids k = ref_kids(A, uc, r, inv, c, tl, true, fast);
+                if (k.ha && k.hb) {
+                    const bool a_first = !(k.tb < k.ta);  // nearer entry first
+                    if (sp < capo) {
+                        stk[sp] = a_first ? k.cb : k.ca;
+                        stt[sp] = f_bf16_down(a_first ? k.tb : k.ta);
+                        sp += stride;
+                    }
+                    cur = a_first ? k.ca : k.cb;
+                } else if (k.ha || k.hb) {
+                    cur = k.ha ? k.ca : k.cb;
                 }
             }
         }
         if (__ballot(count > 0) == 0) return;  // every lane's walk finished
-#if RT_LEAF_PREFETCH
-        // the leaf's records software-pipelined: record i + 1's loads are in flight while
-        // record i is tested (a leaf is a chain of dependent loads otherwise)
-        PrimRec gn;
-        if (count > 0) gn = load_prim(A.prims, start);
-        for (int i = 0; i < count; ++i) {
-            const PrimRec g = gn;
-            if (i + 1 < count) gn = load_prim(A.prims, start + i + 1);
-#else
         for (int i = 0; i < count; ++i) {
             const PrimRec g = load_prim(A.prims, start + i);
-#endif
             if (COUNT) wc.tests++;
             if (WSTAT && first_active()) wc.wtests++;
             if (SHADOW && FLAT_SHADOW) {
@@ -1405,12 +1369,12 @@ __device__ void lane_walk(const AccelPtrs& A, const Ray& r, bool active, float l
 // SPLIT = false compiles the plain walk alone: the split's registers spill in the
 // car's production kernel (+8 % per frame there, r02m), so only the kernels of
 // big scenes (the compacting k_accel instance and k_accel_tail) carry it.
-template <bool SHADOW, bool COUNT = false, bool WSTAT = false, bool SPEC = true, bool MT = false, bool SPLIT = true>
+template <bool SHADOW, bool COUNT = false, bool WSTAT = false, bool MT = false, bool SPLIT = true>
 __device__ __forceinline__ void lane_walk_any(const AccelPtrs& A, Ray& r, bool active, float lim_shadow, Best& b,
                                               bool& shadow, int* stk, unsigned short* stt, int stride, int cap,
                                               WalkCount& wc) {
     if (!SPLIT) {  // the plain walk, without the split's registers
-        lane_walk<SHADOW, COUNT, WSTAT, SPEC, MT, true>(A, r, active, lim_shadow, b, shadow, stk, stt, stride, cap, wc);
+        lane_walk<SHADOW, COUNT, WSTAT, MT, true>(A, r, active, lim_shadow, b, shadow, stk, stt, stride, cap, wc);
         return;
     }
     const unsigned long long m = __ballot(active);
@@ -1432,7 +1396,7 @@ __device__ __forceinline__ void lane_walk_any(const AccelPtrs& A, Ray& r, bool a
            mk(__shfl(r.d.x, src), __shfl(r.d.y, src), __shfl(r.d.z, src))};
     const float ls = __shfl(lim_shadow, src);
     bool sh = false;
-    lane_walk<SHADOW, COUNT, WSTAT, SPEC, MT>(A, rr, walk, ls, b, sh, stk, stt, stride, cap, wc, G, lane % G);
+    lane_walk<SHADOW, COUNT, WSTAT, MT>(A, rr, walk, ls, b, sh, stk, stt, stride, cap, wc, G, lane % G);
     // the group lane holding this lane's result (recomputed here: nothing extra live through the walk)
     const int from = G > 1 ? G * __popcll(__ballot(active) & ((1ull << lane) - 1ull)) : lane;
     if (SHADOW) {
@@ -1652,13 +1616,6 @@ constexpr int kTileRec = 24;
 // Ray compaction (rt_set_tail): queue entries per 64x64-pixel region.
 constexpr int kTailRegion = 64 * 64;
 constexpr size_t kTailAutoItems = 8192;  // RT_TAIL_AUTO threshold
-#ifndef RT_TAIL_ONESHOT
-#define RT_TAIL_ONESHOT 1
-#endif
-// k_accel_tail grid: one wave per possible chunk (64 per region), each taking one, or a
-// resident grid striding over the chunks.
-constexpr bool kTailOneShot = RT_TAIL_ONESHOT != 0;
-
 
 // Cost-ordered dispatch (rt_set_schedule, k_tile_order): 32 half-octave
 // buckets of a tile's work; the render kernel counts them per group of
@@ -1700,7 +1657,7 @@ __device__ __forceinline__ void walk_rec(unsigned long long* rec, int slot, cons
 // One bounce of gpu_shader.comp:450-517 for a wave's rays: closest hit, background
 // on a miss, the shadow ray, then Phong and the mirror ray (shade_bounce).
 // bg_y() gives the lane's image row (recomputed, not kept live through the walks).
-template <bool COUNT, bool SPEC, bool COST, bool MT, bool SPLIT, class BgY>
+template <bool COUNT, bool COST, bool MT, bool SPLIT, class BgY>
 __device__ __forceinline__ void bounce_step(const AccelPtrs& A, const float4* __restrict__ mat, const KParams& kp,
                                             int depth, Ray& ray, bool& alive, V& acc, V& att, BgY bg_y, int* stk,
                                             unsigned short* stt, int cap, WalkCount& wc, unsigned long long* rec,
@@ -1711,8 +1668,8 @@ __device__ __forceinline__ void bounce_step(const AccelPtrs& A, const float4* __
     WalkCount w0 = wc;
     unsigned long long c0 = COUNT ? clock64() : 0;
     if (lane_mode)
-        lane_walk_any<false, COST || COUNT, COUNT, SPEC, MT, SPLIT>(A, ray, alive, 0.f, best, unused, stk, stt,
-                                                                    blockDim.x, cap, wc);
+        lane_walk_any<false, COST || COUNT, COUNT, MT, SPLIT>(A, ray, alive, 0.f, best, unused, stk, stt, blockDim.x,
+                                                              cap, wc);
     else
         packet_walk<false, COST || COUNT, COUNT, MT>(A, ray, alive, 0.f, best, unused, wc);
     if (COUNT) walk_rec(rec, 2 * depth, w0, wc, clock64() - c0);
@@ -1735,8 +1692,8 @@ __device__ __forceinline__ void bounce_step(const AccelPtrs& A, const float4* __
     w0 = wc;
     c0 = COUNT ? clock64() : 0;
     if (depth >= shadow_from)
-        lane_walk_any<true, COST || COUNT, COUNT, SPEC, MT, SPLIT>(A, sr, alive, gmin(ld, 1e20f), dummy, shadow, stk,
-                                                                   stt, blockDim.x, cap, wc);
+        lane_walk_any<true, COST || COUNT, COUNT, MT, SPLIT>(A, sr, alive, gmin(ld, 1e20f), dummy, shadow, stk, stt,
+                                                             blockDim.x, cap, wc);
     else
         packet_walk<true, COST || COUNT, COUNT, MT>(A, sr, alive, gmin(ld, 1e20f), dummy, shadow, wc);
     if (COUNT) walk_rec(rec, 2 * depth + 1, w0, wc, clock64() - c0);
@@ -1750,7 +1707,7 @@ __device__ __forceinline__ void bounce_step(const AccelPtrs& A, const float4* __
 
 // Walk counts (node steps, tests) are kept when COST: they are the cost that
 // orders a later dispatch (rt_set_schedule). COUNT adds the per-walk records.
-template <bool COUNT, bool SPEC, bool COST = true, bool TAIL = false, bool MT = false, bool QUEUE = TAIL>
+template <bool COUNT, bool COST = true, bool TAIL = false, bool MT = false, bool QUEUE = TAIL>
 __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, const KParams& kp, int tile,
                            int part, int* stk, unsigned short* stt, int cap, WalkCount& wc,
                            unsigned long long* rec, bool heavy) {
@@ -1790,9 +1747,9 @@ __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, c
     }
     for (int depth = 0; depth < kp.maxBounces; ++depth) {
         if (__ballot(alive) == 0) break;
-        bounce_step<COUNT, SPEC, COST, MT, TAIL || RT_SPLIT_ALL>(A, mat, kp, depth, ray, alive, acc, att,
-                                       [&]() { return tile_pixel(kp, tile).y; }, stk, stt, cap, wc, rec, lane_from,
-                                       shadow_from);
+        bounce_step<COUNT, COST, MT, TAIL>(A, mat, kp, depth, ray, alive, acc, att,
+                                           [&]() { return tile_pixel(kp, tile).y; }, stk, stt, cap, wc, rec,
+                                           lane_from, shadow_from);
         if (TAIL && QUEUE && depth + 1 == kp.tail_from && __popcll(__ballot(alive)) <= kp.tail_max_lanes) {
             // Compaction: the rays still alive go to the tail queue (one atomic per wave)
             // per 64x64-pixel region (8x8 tiles), so a tail wave's rays come from one area
@@ -1823,15 +1780,9 @@ __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, c
     if (pc.active && mine && !deferred) store_px(kp, pc.r, pc.x, make_float4(acc.x, acc.y, acc.z, 1.0f));
 }
 
-// PERSISTENT: each wave pulls tiles from one device counter until none is
-// left (every wave reaches the exit); otherwise one tile per wave. TIMED
-// writes each tile's start/end wall clock and walk counts (diagnostics only).
-// At most 128 VGPRs: four waves per SIMD, which the LDS stacks also fit
-// (accel.h, kLaneStack).
-#ifndef RT_UNIFORM_TILE
-#define RT_UNIFORM_TILE 0  // tile / part / slot forced into SGPRs in every instance: car +-0, config 2 -1 %,
-                           // latency instance 4 -> 9 spilled VGPRs (r04zz14); off
-#endif
+// One dispatch slot per wave. TIMED writes each tile's start/end wall clock and
+// walk counts (diagnostics only). At most 128 VGPRs: four waves per SIMD, which
+// the LDS stacks also fit (accel.h, kLaneStack).
 #ifndef RT_ACCEL_ATTR
 #define RT_ACCEL_ATTR __attribute__((amdgpu_waves_per_eu(4)))
 #endif
@@ -1839,8 +1790,7 @@ __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, c
 // dispatch records each tile's cost for the next order (rt_set_schedule); without COST
 // it can only record the wall-time cost (kp.cost_time), which needs no counters.
 // TAIL: queue the rays alive after bounce tail_from - 1 for k_accel_tail (rt_set_tail).
-template <bool PERSISTENT, bool TIMED, bool SPEC, bool COST = true, bool TAIL = false, bool MT = false,
-          bool REC = COST, bool QUEUE = TAIL>
+template <bool TIMED, bool COST = true, bool TAIL = false, bool MT = false, bool REC = COST, bool QUEUE = TAIL>
 __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, const float4* __restrict__ mat, KParams kp) {
     extern __shared__ int lds_stack[];
     // per-lane stacks, entry j of lane i at [j * blockDim.x + i]: codes, then bf16 entry parameters
@@ -1849,19 +1799,14 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, con
         reinterpret_cast<unsigned short*>(lds_stack + static_cast<size_t>(kp.lane_stack) * blockDim.x) + threadIdx.x;
     const int lane = threadIdx.x & 63;
     int tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (PERSISTENT) {
-        int t = 0;
-        if (lane == 0) t = atomicAdd(kp.tile_counter, 1);
-        tile = __shfl(t, 0);
-    }
     // dispatch slots: the heavy_k heaviest tiles (the head of the cost order) as heavy_parts
     // waves each, then the rest of the order one wave per tile
     const int hs = kp.heavy_k * kp.heavy_parts;
-    while (tile < kp.tiles + hs - kp.heavy_k) {
+    if (tile < kp.tiles + hs - kp.heavy_k) {
         unsigned long long t0 = 0;
         if (TIMED || (REC && kp.cost_time)) t0 = wall_clock64();
         int part = 0;
-        const int slot = REC || RT_UNIFORM_TILE ? __builtin_amdgcn_readfirstlane(tile) : tile;
+        const int slot = REC ? __builtin_amdgcn_readfirstlane(tile) : tile;
         if (kp.tile_order) {  // dispatch order -> image tile (a permutation)
             if (tile < hs) {
                 part = tile % kp.heavy_parts + 1;
@@ -1870,7 +1815,7 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, con
                 tile = kp.tile_order[tile - hs + kp.heavy_k];
             }
         }
-        if (REC || RT_UNIFORM_TILE) {  // wave-uniform: kept in SGPRs through the walks
+        if (REC) {  // wave-uniform: kept in SGPRs through the walks
             tile = __builtin_amdgcn_readfirstlane(tile);
             part = __builtin_amdgcn_readfirstlane(part);
         }
@@ -1878,8 +1823,8 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, con
         // a split tile's parts stamp records tiles + slot (rt_debug_tile_times with room for them)
         unsigned long long* rec =
             TIMED ? kp.tile_times + kTileRec * static_cast<size_t>(part > 0 ? kp.tiles + slot : tile) : nullptr;
-        accel_tile<TIMED, SPEC, COST, TAIL, MT, QUEUE>(A, mat, kp, tile, part, stk, stt, kp.lane_stack, wc, rec,
-                                                slot < kp.lane_k);
+        accel_tile<TIMED, COST, TAIL, MT, QUEUE>(A, mat, kp, tile, part, stk, stt, kp.lane_stack, wc, rec,
+                                                 slot < kp.lane_k);
         if (TIMED) {
             const unsigned long long t1 = wall_clock64();
             unsigned long long sn = wc.nodes, st = wc.tests, mn = wc.nodes, mt = wc.tests;
@@ -1936,15 +1881,11 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, con
                 atomicAdd(&kp.sched_hist[(tile / kOrderThreads) * kOrderBuckets + work_bucket(wk)], 1u);
             }
         }
-        if (!PERSISTENT) break;
-        int t = 0;
-        if (lane == 0) t = atomicAdd(kp.tile_counter, 1);
-        tile = __shfl(t, 0);
     }
 }
 
-// The queued rays' remaining bounces (rt_set_tail): a resident grid, wave w
-// taking queue chunks w, w + G, ... of 64 rays. The same bounce arithmetic as
+// The queued rays' remaining bounces (rt_set_tail): one wave per possible chunk
+// of 64 rays (kTailRegion / 64 per region), each taking one. The same bounce arithmetic as
 // k_accel; a ray's walk does not depend on the other lanes, so compacting rays
 // from different tiles into one wave leaves every pixel's value unchanged.
 __device__ __forceinline__ int wave_sum_int(int v) {
@@ -1952,7 +1893,6 @@ __device__ __forceinline__ int wave_sum_int(int v) {
     return v;
 }
 
-template <bool SPEC>
 __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel_tail(AccelPtrs A, const float4* __restrict__ mat,
                                                                       KParams kp) {
     extern __shared__ int lds_stack[];
@@ -1960,7 +1900,6 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel_tail(AccelPtrs A
     unsigned short* stt =
         reinterpret_cast<unsigned short*>(lds_stack + static_cast<size_t>(kp.lane_stack) * blockDim.x) + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    const int waves = gridDim.x * (blockDim.x >> 6);
     // chunks of 64 queued rays, region after region: total chunk count first
     int total = 0;
     for (int b = 0; b < kp.tail_regions; b += 64) {
@@ -1970,7 +1909,8 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel_tail(AccelPtrs A
     // (r05: the chunks in XCD-contiguous eighths, each XCD's L2 on one band of regions,
     // measured slower on config 5: 2.734 against 2.689 ms in flight, 3.419 against 3.292
     // solo; profiles/r05zs_abf_tail_xcd_negative_*.json)
-    for (int chunk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); chunk < total; chunk += waves) {
+    const int chunk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (chunk < total) {
         // the region holding chunk: running prefix of the regions' chunk counts
         int rid = 0, first = 0, n = 0, acc0 = 0;
         for (int b = 0; b < kp.tail_regions; b += 64) {
@@ -2011,12 +1951,11 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel_tail(AccelPtrs A
         WalkCount wc{0u, 0u, 0u, 0u};
         for (int depth = kp.tail_from; depth < kp.maxBounces; ++depth) {
             if (__ballot(alive) == 0) break;
-            bounce_step<false, SPEC, false, false, true>(A, mat, kp, depth, ray, alive, acc, att,
-                                            [&]() { return image_row(kp, r); }, stk, stt, kp.lane_stack, wc, nullptr,
-                                            kp.lane_from_depth, kp.shadow_lane_from);
+            bounce_step<false, false, false, true>(A, mat, kp, depth, ray, alive, acc, att,
+                                                   [&]() { return image_row(kp, r); }, stk, stt, kp.lane_stack, wc,
+                                                   nullptr, kp.lane_from_depth, kp.shadow_lane_from);
         }
         if (have) store_px(kp, r, x, make_float4(acc.x, acc.y, acc.z, 1.0f));
-        if (kTailOneShot) break;  // one chunk per wave: no loop-carried state
     }
     if (blockIdx.x == 0)
         for (int b = threadIdx.x; b < kp.tail_counters; b += blockDim.x) kp.tail_count_next[b] = 0;
@@ -2920,12 +2859,10 @@ struct rt_ctx {
     size_t img_pitch = 0;
     int img_w = 0, img_h = 0;
     unsigned long long* stats_dev = nullptr;
-    // launch shape of k_accel (rt_set_launch)
-    int waves_per_block = 1, persistent = 0, cu_count = 256;
+    int cu_count = 256;
     int lane_from_depth = -1;  // bounces >= this use the per-lane walk (0: all, large: none;
                                // -1: auto, see walk_from)
     int cone_cull = 1;
-    int spec_mode = 1;  // speculative while-while in lane_walk (rt_debug_spec): 1 on, 0 off
     int split_max = kSplitMax, split_g = kSplitGroup;  // split per-lane walks (rt_debug_split)
     int heavy_k = kHeavyTiles, heavy_parts = kHeavyParts;  // heaviest tiles as several waves (rt_debug_heavy)
     int lane_k = -1, lane_k_mode = 2;  // heaviest slots' walk modes (rt_debug_lane_k; -1: auto)
@@ -2972,7 +2909,6 @@ struct rt_ctx {
     int shadow_walk_override = -1;  // rt_debug_shadow_walk (-1: policy)
     int tail_parity = 0;
     int lane_stack_override = 0;  // diagnostics only (rt_debug_lane_stack): breaks exactness if too small
-    int* tile_counter = nullptr;
     unsigned long long* tile_times = nullptr;  // diagnostics (rt_debug_tile_times)
     size_t tile_times_cap = 0;
     // animation (rt_set_animated / rt_animate) and the reference's own uploads
@@ -4411,11 +4347,8 @@ void inherit(rt_ctx* b, const rt_ctx* c) {
     b->have_cam = b->have_light = true;
     b->params = c->params;
     b->kernel = RT_KERNEL_ACCEL;
-    b->waves_per_block = c->waves_per_block;
-    b->persistent = c->persistent;
     b->lane_from_depth = c->lane_from_depth;
     b->cone_cull = c->cone_cull;
-    b->spec_mode = c->spec_mode;
     b->split_max = c->split_max;
     b->split_g = c->split_g;
     b->heavy_k = c->heavy_k;
@@ -4627,22 +4560,10 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
         c->have_sched_cam = true;
         const int period = c->moving ? c->moving_period : c->sched_period;
         const int dilate = c->moving ? c->moving_dilate : c->cost_dilate;
-        k2.tile_counter = c->tile_counter;
         k2.tile_times = c->tile_times;
         if (c->tile_times)
             HIP_TRY(hipMemsetAsync(c->tile_times, 0, kTileRec * c->tile_times_cap * sizeof(unsigned long long),
                                    c->stream));
-        const int wpb = c->waves_per_block;
-        int blocks = (k2.tiles + wpb - 1) / wpb;
-        if (c->persistent) {
-            HIP_TRY(hipMemsetAsync(c->tile_counter, 0, 16, c->stream));
-            blocks = std::min(blocks, c->cu_count * 20 / wpb);  // resident at 5 waves/SIMD
-        }
-        const bool spec = c->spec_mode != 0;  // speculative while-while (lane_walk)
-        auto kfn = spec ? (c->persistent ? (c->tile_times ? k_accel<true, true, true> : k_accel<true, false, true>)
-                                         : (c->tile_times ? k_accel<false, true, true> : k_accel<false, false, true>))
-                        : (c->persistent ? (c->tile_times ? k_accel<true, true, false> : k_accel<true, false, false>)
-                                         : (c->tile_times ? k_accel<false, true, false> : k_accel<false, false, false>));
         k2.tile_order = nullptr;
         k2.tile_cost = nullptr;
         k2.heavy_k = 0;
@@ -4716,7 +4637,7 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
         }
         // LDS stacks for the per-lane walks (also those of the lane_k slots)
         const size_t lds = std::min(k2.lane_from_depth, k2.shadow_lane_from) < k2.maxBounces || k2.lane_k > 0
-                               ? static_cast<size_t>(k2.lane_stack) * 64 * wpb * 6
+                               ? static_cast<size_t>(k2.lane_stack) * 64 * 6
                                : 0;
         if (k2.tile_order && k2.tile_order == c->sched_order) {
             // heavy tiles: explicit (rt_debug_heavy) or auto. A frame of at most
@@ -4783,7 +4704,7 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
             // (config 2, the MT car; r04zz profiles), and in flight the ranking matters less.
             const bool whole = k2.tile_cost && c->cost_time != 0 && !c->tile_times && latency &&
                                !(c->moving && c->moving_split);
-            if (!c->persistent && stamps_fit && hp > 1 && hk > 0 && !whole) {
+            if (stamps_fit && hp > 1 && hk > 0 && !whole) {
                 k2.heavy_k = std::min(hk, k2.tiles);
                 k2.heavy_parts = hp;
             }
@@ -4806,8 +4727,6 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
         // Animated scenes keep the scene tree: rt_animate refits its boxes and items (prepare_animation).
         // (off while a rebuild for node boxes that stopped nesting runs: st_suspended)
         const int troot = c->tree_mode == RT_TREE_SCENE && !c->st_suspended ? c->st_root : kNoChild;
-        // production shape on a dispatch that records no tile work: the counter-free kernel
-
         const AccelPtrs A{c->anodes, c->prims, c->lnodes, c->wnodes, c->tleaf, c->titems, troot,
                           c->scene_stack > 0 ? c->scene_stack : kMaxStack, c->nfew, kp.N, c->accel.origin_lim,
                           c->boxes_finite, c->split_max, c->split_g, c->prim_idx_dev,
@@ -4821,7 +4740,7 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
                                   : (c->accel.st.item_ref.size() >= kTailAutoItems ? 2 : 0);
         // the queue's pixel word is row * width + x in 32 bits (rt_device.h): larger
         // frames render without compaction
-        const bool tail = tail_from > 0 && tail_from < k2.maxBounces && !c->persistent &&
+        const bool tail = tail_from > 0 && tail_from < k2.maxBounces &&
                           static_cast<unsigned long long>(k2.width) * k2.out_rows < (1ull << 32);
         const int rx = (k2.tiles_x + 7) / 8, regions = rx * ((k2.tiles / k2.tiles_x + 7) / 8);
         if (tail) {
@@ -4854,50 +4773,45 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
             k2.tail_counters = c->tail_regions_cap;
             k2.tail_max_lanes = c->tail_max_lanes;
         }
+        // The k_accel instance <TIMED, COST, TAIL, MT, REC, QUEUE>. A dispatch that records
+        // no tile work runs without the walk counters (COST); one that records wall-time
+        // costs (cost_time) records them without counters (REC alone).
+        auto kfn = k_accel<false>;  // records the walk counters as the tiles' costs
         if (c->accel.mt) {
             // Moller-Trumbore accelerator: its own instances; no compaction
             k2.tail_queue = nullptr;
-            // a dispatch recording wall-time costs: the counter-free instance that records
-            kfn = spec ? (!k2.tile_cost   ? k_accel<false, false, true, false, false, true>
-                          : k2.cost_time ? k_accel<false, false, true, false, false, true, true>
-                                         : k_accel<false, false, true, true, false, true>)
-                       : (!k2.tile_cost   ? k_accel<false, false, false, false, false, true>
-                          : k2.cost_time ? k_accel<false, false, false, false, false, true, true>
-                                         : k_accel<false, false, false, true, false, true>);
-            blocks = (k2.tiles + wpb - 1) / wpb;
-        } else if (kfn == k_accel<false, false, true>) {
-            // production shape: the counter-free kernel on a dispatch that records no tile
-            // work; the queueing kernel when the tail runs (other shapes: no compaction)
-            if (tail || latency) {
-                // the compacting instance; in latency mode without a queue (tail_from 0), for
-                // its split walks in sparse waves (lane_walk_any), which the production
-                // instance leaves out for its registers
-                // (latency mode without compaction: the instance without the queue's code)
-                if (tail)
-                    kfn = !k2.tile_cost  ? k_accel<false, false, true, false, true>
-                          : k2.cost_time ? k_accel<false, false, true, false, true, false, true>
-                                         : k_accel<false, false, true, true, true>;
-                else
-                    kfn = !k2.tile_cost  ? k_accel<false, false, true, false, true, false, false, false>
-                          : k2.cost_time ? k_accel<false, false, true, false, true, false, true, false>
-                                         : k_accel<false, false, true, true, true, false, true, false>;
-            } else if (!k2.tile_cost) {
-                kfn = k_accel<false, false, true, false>;
-            } else if (k2.cost_time) {
-                kfn = k_accel<false, false, true, false, false, false, true>;  // records, no counters
-            }
-        } else if (tail) {
+            kfn = !k2.tile_cost  ? k_accel<false, false, false, true>
+                  : k2.cost_time ? k_accel<false, false, false, true, true>
+                                 : k_accel<false, true, false, true>;
+        } else if (c->tile_times) {
+            // per-tile records (rt_debug_tile_times): counters on, no compaction
             k2.tail_queue = nullptr;
+            kfn = k_accel<true>;
+        } else if (tail) {
+            // the compacting instance, with the split walks of sparse waves (lane_walk_any)
+            // that the production instance leaves out for its registers
+            kfn = !k2.tile_cost  ? k_accel<false, false, true>
+                  : k2.cost_time ? k_accel<false, false, true, false, true>
+                                 : k_accel<false, true, true>;
+        } else if (latency) {
+            // latency mode without compaction (tail_from 0): the same split walks, without
+            // the queue's code
+            kfn = !k2.tile_cost  ? k_accel<false, false, true, false, false, false>
+                  : k2.cost_time ? k_accel<false, false, true, false, true, false>
+                                 : k_accel<false, true, true, false, true, false>;
+        } else if (!k2.tile_cost) {
+            kfn = k_accel<false, false>;  // production
+        } else if (k2.cost_time) {
+            kfn = k_accel<false, false, false, false, true>;  // production, recording wall time
         }
         const bool tail_on = k2.tail_queue != nullptr;
-        if (!c->persistent)  // every dispatch slot: the split heavy tiles' extra waves too
-            blocks = (k2.tiles + k2.heavy_k * (k2.heavy_parts - 1) + wpb - 1) / wpb;
-        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(64 * wpb), lds, c->stream, A, c->mat, k2);
+        // one wave per dispatch slot: the split heavy tiles' extra waves too
+        const int blocks = k2.tiles + k2.heavy_k * (k2.heavy_parts - 1);
+        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(64), lds, c->stream, A, c->mat, k2);
         if (tail_on) {
             const size_t tlds = static_cast<size_t>(k2.lane_stack) * 64 * 6;
-            const int tgrid = kTailOneShot ? regions * (kTailRegion / 64) : c->cu_count * 16;
-            hipLaunchKernelGGL(spec ? k_accel_tail<true> : k_accel_tail<false>, dim3(tgrid), dim3(64), tlds,
-                               c->stream, A, c->mat, k2);
+            const int tgrid = regions * (kTailRegion / 64);  // one wave per possible chunk
+            hipLaunchKernelGGL(k_accel_tail, dim3(tgrid), dim3(64), tlds, c->stream, A, c->mat, k2);
             c->tail_parity = 1 - c->tail_parity;
         }
         if (k2.tile_cost) {
@@ -5033,8 +4947,7 @@ int rtx::create_ctx(rt_ctx** out, int device, hipStream_t stream) {
     c->stream = stream;
     if (set_dev(c) != RT_OK || (!stream && rtx::make_stream(&c->stream, env_cumask()) != hipSuccess) ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-        hipMalloc(&c->stats_dev, ST_COUNT * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(&c->tile_counter, 16) != hipSuccess) {
+        hipMalloc(&c->stats_dev, ST_COUNT * sizeof(unsigned long long)) != hipSuccess) {
         rt_destroy(c);
         return RT_ERR_DEVICE;
     }
@@ -5126,7 +5039,6 @@ int rt_destroy(rt_ctx* c) {
     hipFree(c->staging_idx);
     hipFree(c->img);
     hipFree(c->stats_dev);
-    hipFree(c->tile_counter);
     hipFree(c->tail_queue);
     hipFree(c->tail_counts);
     hipFree(c->tile_times);
@@ -5910,20 +5822,6 @@ extern "C" int rt_debug_split(rt_ctx* c, int max_rays, int group) {
     if (!c || max_rays < 0 || max_rays > 32 || group < 2 || group > 64 || (group & (group - 1))) return RT_ERR_INVALID;
     c->split_max = max_rays;
     c->split_g = group;
-    return RT_OK;
-}
-
-// Diagnostics: speculative while-while in the per-lane walk (1 on, the default; 0 off).
-extern "C" int rt_debug_spec(rt_ctx* c, int mode) {
-    if (!c || mode < 0 || mode > 1) return RT_ERR_INVALID;
-    c->spec_mode = mode;
-    return RT_OK;
-}
-
-extern "C" int rt_set_launch(rt_ctx* c, int waves_per_block, int persistent) {
-    if (!c || (waves_per_block != 1 && waves_per_block != 2 && waves_per_block != 4)) return RT_ERR_INVALID;
-    c->waves_per_block = waves_per_block;
-    c->persistent = persistent ? 1 : 0;
     return RT_OK;
 }
 

@@ -210,7 +210,6 @@ RT_SYMBOLS = {
     "rt_last_kernel_ms": (_I, [_P, _P]),
     "rt_kernel_times": (_I, [_P, _P, _I]),
     "rt_accel_info_get": (_I, [_P, _P]),
-    "rt_set_launch": (_I, [_P, _I, _I]),
     "rt_set_walk": (_I, [_P, _I]),
     "rt_set_tree": (_I, [_P, _I]),
     "rt_build_lbvh": (_I, [_P, _P]),
@@ -676,9 +675,6 @@ class ComputeShader:
             raise RTError("rt_kernel_times", n)
         return buf[:min(n, cap)].copy()
 
-    def set_launch(self, waves_per_block=4, persistent=False):
-        self._chk(self._lib.rt_set_launch(self._h, int(waves_per_block), int(bool(persistent))), "rt_set_launch")
-
     def set_walk(self, lane_from_depth):
         self._chk(self._lib.rt_set_walk(self._h, int(lane_from_depth)), "rt_set_walk")
 
@@ -779,11 +775,6 @@ class ComputeShader:
         fn.argtypes = [_P]
         fn.restype = _I
         return int(fn(self._h))
-
-    def debug_spec(self, mode):
-        fn = self._lib.rt_debug_spec
-        fn.argtypes = [_P, _I]
-        self._chk(fn(self._h, int(mode)), "rt_debug_spec")
 
     def debug_split(self, max_rays, group=8):
         """Split per-lane walks of waves with <= max_rays rays over groups of <= group lanes (0: off)."""

@@ -460,6 +460,32 @@ def test_cost_schedule_identical_images(ctx, sched):
 
 
 @pytest.mark.gpu
+def test_tile_times_identical_image(ctx):
+    """rt_debug_tile_times: the instance of k_accel that stamps a record per tile renders
+    the default frame bit for bit (the car at 160x90, 20 x 12 tiles, a record for each),
+    and every tile's record holds its wave's wall clock: end >= start > 0."""
+    W, H = 160, 90
+    tiles = ((W + 7) // 8) * ((H + 7) // 8)
+    fs = rtamd.generate(3, 0, W, H)
+    ctx.upload(fs)
+    ctx.set_params(W, H, 3, True)
+    ctx.set_kernel(rtamd.KERNEL_ACCEL)
+    try:
+        ref = ctx.render(W, H)
+        ctx.debug_tile_times(tiles)
+        img = ctx.render(W, H)
+        rec = ctx.tile_times(tiles)
+    finally:
+        ctx.debug_tile_times(0)
+        ctx.set_kernel(rtamd.KERNEL_AUTO)
+    assert np.array_equal(img, ref), f"timed frame: {int((img != ref).any(axis=-1).sum())} px differ"
+    assert rec.shape == (tiles, 24)
+    start, end = rec[:, 0], rec[:, 1]
+    assert (start > 0).all(), f"{int((start == 0).sum())} tiles without a start stamp"
+    assert (end >= start).all(), f"{int((end < start).sum())} tiles end before they start"
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("cfg,W,H,mb", [(2, 400, 300, 1), (3, 640, 360, 3), (5, 320, 180, 3), (3, 3840, 2160, 3)])
 def test_latency_mode_exact(ctx, cfg, W, H, mb):
     """rt_set_latency_mode: the split-walk instance without a queue and the heaviest tiles

@@ -19,34 +19,29 @@ import rtamd  # noqa: E402
 
 WL = {2: (2, 800, 600, 1), 3: (3, 1920, 1080, 3), 4: (3, 3840, 2160, 3), 5: (5, 1920, 1080, 3)}
 VARIANTS = {
-    "default": dict(kernel=0, wpb=1, persistent=False, walk=1),
-    "hybrid_w2": dict(kernel=3, wpb=2, persistent=False, walk=1),
-    "hybrid_w4": dict(kernel=3, wpb=4, persistent=False, walk=1),
-    "lane_all": dict(kernel=3, wpb=1, persistent=False, walk=0),
-    "packet_all": dict(kernel=3, wpb=1, persistent=False, walk=99),
-    "lane_from2": dict(kernel=3, wpb=1, persistent=False, walk=2),
-    "persistent": dict(kernel=3, wpb=1, persistent=True, walk=1),
-    "nocone": dict(kernel=3, wpb=1, persistent=False, walk=1, cone=0),
-    "packet": dict(kernel=2, wpb=4, persistent=False, walk=1),
-    "lpt": dict(kernel=3, wpb=1, persistent=False, walk=1, order="lpt"),
-    "mix1": dict(kernel=3, wpb=1, persistent=False, walk=1, order="mix1"),
-    "mix3": dict(kernel=3, wpb=1, persistent=False, walk=1, order="mix3"),
-    "mix7": dict(kernel=3, wpb=1, persistent=False, walk=1, order="mix7"),
-    "rows": dict(kernel=3, wpb=1, persistent=False, walk=1, sched=0),
-    "spec_on": dict(kernel=3, wpb=1, persistent=False, walk=1, spec=1),
-    "spec_off": dict(kernel=3, wpb=1, persistent=False, walk=1, spec=0),
-    "lpt_rows": dict(kernel=3, wpb=1, persistent=False, walk=1, order="rows"),
-    "stack20": dict(kernel=3, wpb=1, persistent=False, walk=1, stack=20),
-    "stack16": dict(kernel=3, wpb=1, persistent=False, walk=1, stack=16),
-    "reftree": dict(kernel=3, wpb=1, persistent=False, walk=1, tree=0),
-    "reftree_lane": dict(kernel=3, wpb=1, persistent=False, walk=0, tree=0),
+    "default": dict(kernel=0, walk=1),
+    "lane_all": dict(kernel=3, walk=0),
+    "packet_all": dict(kernel=3, walk=99),
+    "lane_from2": dict(kernel=3, walk=2),
+    "nocone": dict(kernel=3, walk=1, cone=0),
+    "packet": dict(kernel=2, walk=1),
+    "lpt": dict(kernel=3, walk=1, order="lpt"),
+    "mix1": dict(kernel=3, walk=1, order="mix1"),
+    "mix3": dict(kernel=3, walk=1, order="mix3"),
+    "mix7": dict(kernel=3, walk=1, order="mix7"),
+    "rows": dict(kernel=3, walk=1, sched=0),
+    "lpt_rows": dict(kernel=3, walk=1, order="rows"),
+    "stack20": dict(kernel=3, walk=1, stack=20),
+    "stack16": dict(kernel=3, walk=1, stack=16),
+    "reftree": dict(kernel=3, walk=1, tree=0),
+    "reftree_lane": dict(kernel=3, walk=0, tree=0),
 }
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", type=int, default=3)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--frames", type=int, default=20)
-ap.add_argument("--variants", default="default,lane_all,packet_all,hybrid_w2")
+ap.add_argument("--variants", default="default,lane_all,packet_all")
 ap.add_argument("--bounces", type=int, default=0, help="override maxBounces")
 ap.add_argument("--times", action="store_true", help="per-tile wall-clock distribution")
 ap.add_argument("--lib2", default=None, help="second librtamd.so build: variants NAME@2 run on it")
@@ -106,15 +101,12 @@ for rnd in range(a.rounds):
     for n in names:
         ctx, v = pick(n)
         ctx.set_kernel(v["kernel"])
-        ctx.set_launch(v["wpb"], v["persistent"])
         ctx.set_walk(v["walk"])
         ctx.debug_cone_cull(v.get("cone", 1))
         if hasattr(ctx._lib, "rt_debug_tile_order"):
             ctx.debug_tile_order(orders.get(v.get("order")))
         if hasattr(ctx._lib, "rt_set_schedule"):
             ctx.set_schedule(v.get("sched", 1))
-        if hasattr(ctx._lib, "rt_debug_spec"):
-            ctx.debug_spec(v.get("spec", 1))
         if hasattr(ctx._lib, "rt_debug_lane_stack"):
             ctx.debug_lane_stack(v.get("stack", 0))
         if hasattr(ctx._lib, "rt_set_tree"):
@@ -137,15 +129,12 @@ if a.times:
     for n in names:
         ctx, v = pick(n)
         ctx.set_kernel(v["kernel"])
-        ctx.set_launch(v["wpb"], v["persistent"])
         ctx.set_walk(v["walk"])
         ctx.debug_cone_cull(v.get("cone", 1))
         if hasattr(ctx._lib, "rt_debug_tile_order"):
             ctx.debug_tile_order(orders.get(v.get("order")))
         if hasattr(ctx._lib, "rt_set_schedule"):
             ctx.set_schedule(v.get("sched", 1))
-        if hasattr(ctx._lib, "rt_debug_spec"):
-            ctx.debug_spec(v.get("spec", 1))
         if hasattr(ctx._lib, "rt_debug_lane_stack"):
             ctx.debug_lane_stack(v.get("stack", 0))
         if hasattr(ctx._lib, "rt_set_tree"):

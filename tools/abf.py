@@ -26,7 +26,7 @@ ap.add_argument("--inflight", type=int, default=2)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--frames", type=int, default=200)
 ap.add_argument("--walk2", type=int, default=-1, help="walk policy (rt_set_walk) for the lib2 runs")
-ap.add_argument("--set2", default="", help="lib2 settings, e.g. schedule=0,launch=2,walk=0")
+ap.add_argument("--set2", default="", help="lib2 settings, e.g. schedule=0,walk=0")
 ap.add_argument("--set", default="", help="settings for both builds, e.g. latency=1")
 ap.add_argument("--nocheck", action="store_true", help="timing only: images may differ (experiments)")
 ap.add_argument("--bounces", type=int, default=0, help="override maxBounces")
@@ -76,9 +76,9 @@ for _ in range(F):
     for kv in ",".join(sets).split(",") if sets else []:
         if True:
             k, v = kv.split("=")
-            {"schedule": lambda x: c.set_schedule(x), "launch": lambda x: c.set_launch(x, False),
-             "persistent": lambda x: c.set_launch(1, bool(x)), "period": lambda x: c.debug_sched_period(x), "tail": lambda x: c.set_tail(x), "tlanes": lambda x: c.debug_tail_lanes(x), "shwalk": lambda x: c.debug_shadow_walk(x),
-             "spec": lambda x: c.debug_spec(x), "stack": lambda x: c.debug_lane_stack(x),
+            {"schedule": lambda x: c.set_schedule(x),
+             "period": lambda x: c.debug_sched_period(x), "tail": lambda x: c.set_tail(x), "tlanes": lambda x: c.debug_tail_lanes(x), "shwalk": lambda x: c.debug_shadow_walk(x),
+             "stack": lambda x: c.debug_lane_stack(x),
              "walk": lambda x: c.set_walk(x), "tree": lambda x: c.set_tree(x),
              "latency": lambda x: c.set_latency_mode(x), "cone": lambda x: c.debug_cone_cull(x),
              "heavy": lambda x: c.debug_heavy(x // 100, x % 100), "costtime": lambda x: c.debug_cost_time(x),
