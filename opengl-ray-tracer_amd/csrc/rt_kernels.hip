@@ -2167,8 +2167,6 @@ struct RefitArgs {
     const float4* gbox;        // per entry with AF_BOX: its growth box (lo, hi; pinned), or null
     const FlatNode* nsrc;      // rt_update_nodes: the host's node records (pinned), or null
     int* report;               // pinned: set to 1 when an entry's bound changed kind
-    unsigned* ctr;             // [0] workgroup tickets, [1] finished record workgroups, then the flags
-    unsigned tbase, abase;     // their values before this launch
     int na, nd, nb;            // workgroups of the record, node-set and node roles
     const int4* dirty;         // slot refit work list (n_dirty entries after the nb node waves, + 1 end)
     int n_big;                 // its first n_big slots take a workgroup each, the rest a wave each
@@ -2177,7 +2175,6 @@ struct RefitArgs {
     int n_dirty, rec;          // its length; the wide record size (kWideRec / kWideRecMt)
     const int* titem_ref;      // per scene-tree item: its reference leaf
     int n_items, N;
-    int wait;                  // node / slot roles wait for the record role: 1 by tickets, 2 in start order
     int direct;                // node / slot roles derive the entries' boxes from `fresh` themselves
 };
 
@@ -2217,9 +2214,8 @@ __device__ __forceinline__ void wave_minmax(float lo[3], float hi[3]) {
 // wave_minmax over the workgroup (up to kRefitWaves waves; every thread gets the
 // result); sh: LDS scratch of the workgroup, free again on return.
 constexpr int kRefitWaves = 4;
-constexpr int kRefitFlag0 = 16, kRefitFlags = 16;  // k_refit's all-done flags: ctr[16 + 16 k]
-constexpr long long kDirectReads = 2048;           // rt_ctx::refit_mode auto
-constexpr int kBigList = 256;                      // a slot's refit list a wave unions in one step
+constexpr long long kDirectReads = 2048;  // rt_ctx::refit_mode auto
+constexpr int kBigList = 256;             // a slot's refit list a wave unions in one step
 __device__ __forceinline__ void block_minmax(float lo[3], float hi[3], float (*sh)[6]) {
     wave_minmax(lo, hi);
     const int nw = blockDim.x >> 6;
@@ -2681,53 +2677,25 @@ __device__ void refit_slot(const AnimMaps& m, const AnimOut& o, const RefitArgs&
 //   [na, na + nd)       node-set role (set_node), a lane per node or item;
 //   [na + nd, ...)      a workgroup each: node role (grow_node) for the first nb, then
 //                       slot role (refit_slot); both read what the record role wrote.
-// Modes (rt_debug_refit), on the car's wheels (640 entries, 650 dirty slots):
-//   1 default: two launches, records and node sets in one-wave workgroups, then nodes
-//     and slots in kRefitWaves-wave ones: the kernel boundary orders them (11.4 + 8.4
-//     us, no gap between them; r05n);
-//   3 ONE launch of kRefitWaves-wave workgroups whose node / slot workgroups wait (wait
-//     2) until every record workgroup has released its writes. Workgroups start in
-//     index order, record workgroups first, and every one of them runs to its end
-//     without waiting, so the waits end. Measured 42 us polling the done counter, 52
-//     us polling kRefitFlags copies of a flag (r05o, r05p), 29 us with one agent-scope
-//     fence per workgroup instead of one per thread (each writes back or invalidates the
-//     XCD's L2; r05zv): slower than two launches;
-//   0 as 3 with the start order made explicit by a ticket per workgroup (wait 1): the
-//     ticket counter serialises the launch (35 us when measured with one-wave slots);
+// Launch shapes (rt_debug_refit), on the car's wheels (640 entries, 650 dirty slots):
+//   1 two launches, records and node sets in one-wave workgroups, then nodes and slots
+//     in kRefitWaves-wave ones: the kernel boundary orders them (11.4 + 8.4 us, no gap
+//     between them; r05n);
 //   2 one launch whose node / slot roles derive each entry's boxes from its record over
-//     the host link themselves (direct; 72 us).
-// Copying the records to the device before the launches instead of reading them over
-// the host link measured no faster (r05k: waited car frame 0.259 against 0.252 ms). The
-// record role's 11 us are not its stores: with every store skipped in turn (timing builds,
-// r05x) it took 10.0-12.2 us, and moved beside the slot roles (its boxes alone in the first
-// launch, r05y) the first launch still took 10.3 us while the second grew to 23.
+//     the host link themselves (direct; 72 us on the car, 4 us less than mode 1 for a
+//     few records: what the auto policy picks up to kDirectReads).
+// Tried and removed: one launch whose node / slot workgroups waited on a flag in global
+// memory for the record workgroups (29-52 us, and the wait relied on a start order HIP
+// does not promise; profiles/r05x_refit_record_probe.txt, r06_anim_probe_modes.txt), and
+// the records copied to the device first (no faster). CHANGELOG has the measurements.
 // The node-set role never runs with AF_GROW entries in the same flush (flush_updates
 // applies host node records first), so no two roles write the same box.
 __global__ __launch_bounds__(64 * kRefitWaves) void k_refit(AnimMaps m, AnimOut o, RefitArgs r) {
     __shared__ float sh[kRefitWaves][6];
     const int tid = threadIdx.x, nt = blockDim.x;
-    unsigned t = blockIdx.x;  // without waits the start order does not matter
-    if (r.wait == 1) {
-        __shared__ unsigned ticket;
-        if (tid == 0) ticket = __hip_atomic_fetch_add(r.ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - r.tbase;
-        __syncthreads();
-        t = ticket;
-    }
+    unsigned t = blockIdx.x;
     if (t < static_cast<unsigned>(r.na)) {
         refit_record(m, o, r, static_cast<int>(t) * nt + tid);
-        if (r.wait) {
-            // the workgroup's writes complete (barrier), then ONE agent-scope release: each
-            // fence writes the XCD's L2 back, and one per thread cost the launch ~30 us
-            __syncthreads();
-            if (tid == 0) {
-                __threadfence();
-                const unsigned done = __hip_atomic_fetch_add(r.ctr + 1, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-                if (done - r.abase == static_cast<unsigned>(r.na) - 1u)  // the last one: raise the flags
-                    for (int k = 0; k < kRefitFlags; ++k)
-                        __hip_atomic_store(r.ctr + kRefitFlag0 + 16 * k, r.abase + r.na, __ATOMIC_RELEASE,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
         return;
     }
     t -= r.na;
@@ -2736,28 +2704,6 @@ __global__ __launch_bounds__(64 * kRefitWaves) void k_refit(AnimMaps m, AnimOut 
         return;
     }
     t -= r.nd;
-    if (r.wait) {
-        // one of kRefitFlags copies of the all-done flag, a cache line each: ~650 waiting
-        // workgroups polling the counter itself held its increments back (car: 42 us)
-        const unsigned* flag = r.ctr + kRefitFlag0 + 16 * (blockIdx.x % kRefitFlags);
-        if (tid == 0) {
-            // Bounded (diagnostic modes only): these waits rely on the record
-            // workgroups having started, which HIP does not promise. Past ~1 s of the
-            // constant-rate clock (100 MHz) the wait gives up and reports, so a scheduling
-            // change shows up as a rebuild (check_reports), not as a GPU hang.
-            const unsigned long long t0 = wall_clock64();
-            while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - r.abase <
-                   static_cast<unsigned>(r.na)) {
-                __builtin_amdgcn_s_sleep(2);
-                if (wall_clock64() - t0 > 100000000ull) {
-                    __hip_atomic_store(r.report, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    break;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // one invalidation per workgroup
-        }
-        __syncthreads();
-    }
     const int w = static_cast<int>(t) - r.nb;
     if (w < 0) {
         grow_node(m, o, r, w + r.nb, sh);
@@ -2793,15 +2739,6 @@ struct rt_ctx {
     bool own_stream = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;      // used once the ring is full
     hipEvent_t sync_ev = nullptr;                  // rt_sync's poll target
-    // The cost order's kernels (k_cost_dilate, k_tile_order) on a second stream behind the
-    // render's end event (rt_debug_order_stream; 0: on this stream, 1: latency-mode
-    // dispatches, 2: all), so that a waited frame ends with its render; the next accelerated
-    // dispatch waits for order_done (join_order), anything that frees or reads the order's
-    // buffers on the host synchronizes order_stream first (sync_order).
-    hipStream_t order_stream = nullptr;
-    hipEvent_t order_ready = nullptr, order_done = nullptr;
-    bool order_pending = false;  // order_done not yet waited for on `stream`
-    int order_mode = 0;
     // rt_sync_frame: a latency-mode cost frame records frame_ev between its render and the
     // order's kernels (same stream), and the waited frame ends there (rt_debug_frame_event)
     int frame_event = 1;
@@ -2930,18 +2867,14 @@ struct rt_ctx {
     bool nodes_rebuild = false;         // host_nodes break a condition the accelerator was built on
     bool bounds_rebuild = false;        // a refit reported a shape whose bound changed kind
     int updates_flushed = 0;            // flushes that refit instead of rebuilding (diagnostics)
-    // rt_debug_refit: 0 one launch (box roles wait on tickets), 1 two launches (default:
-    // the car's waited animated frame 0.262 ms against 0.268 and 0.299, r05d), 2 one
-    // launch (box roles read the records over the host link themselves)
-    // rt_debug_refit; -1 auto: one direct launch (mode 2) while the records its readers
-    // fetch over the host link are few (direct_reads <= kDirectReads), else two launches
-    // (mode 1). Waited animated frames, mode 1 against 2: config 2's three spheres (~50
-    // reads) 0.1062 against 0.1024 ms; the car's wheels (~7,500 reads) 0.2449 against
-    // 0.2777 (r05q)
+    // rt_debug_refit: 1 two launches (records and node sets, then the box roles), 2 one
+    // launch (box roles read the records over the host link themselves); -1 auto: mode 2
+    // while the records its readers fetch over the host link are few (direct_reads <=
+    // kDirectReads), else mode 1. Waited animated frames, mode 1 against 2: config 2's
+    // three spheres (~50 reads) 0.1062 against 0.1024 ms; the car's wheels (~7,500 reads)
+    // 0.2449 against 0.2777 (r05q)
     int refit_mode = -1;
     long long direct_reads = 0, n_direct_slot_reads = 0;
-    char* refit_dev = nullptr;  // refit mode 4: the pinned slot's records copied to the device
-    size_t refit_dev_cap = 0;
     long long dirty_sum = 0;  // rt_debug_refit_stats: the slot refit's prim ranges (largest, total)
     long long last_flush_bytes = 0;  // rt_debug_refit_stats: the pinned records of the last flush
     int refit_compactions = 0;       // rt_debug_refit_stats: stale entries dropped (compact_refit_set)
@@ -2969,8 +2902,6 @@ struct rt_ctx {
     // the slot is wanted back. A wait that drains the stream (rt_sync) retires it
     // unrecorded (stream_drained).
     int mark_slot = -1;
-    unsigned* refit_ctr = nullptr;      // k_refit's ticket and done counters (never reset)
-    unsigned ctr_tickets = 0, ctr_done = 0;  // their values after the last launch
     int anim_slot = 0;
     float4* anim_sbox = nullptr;        // per animated shape boxes (AnimOut::sbox)
     size_t anim_sbox_cap = 0;
@@ -3962,32 +3893,11 @@ void stream_drained(rt_ctx* c) {
 // hipStreamSynchronize of the context's stream, which also retires its refit slots
 // (and its sub-contexts', which run on the same stream).
 hipError_t sync_stream(rt_ctx* c) {
-    hipError_t e = hipStreamSynchronize(c->stream);
-    for (rt_ctx* x : {c, c->brute, c->mtc})
-        if (e == hipSuccess && x && x->order_stream) {
-            e = hipStreamSynchronize(x->order_stream);
-            if (e == hipSuccess) x->order_pending = false;
-        }
+    const hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess)
         for (rt_ctx* x : {c, c->brute, c->mtc})
             if (x) stream_drained(x);
     return e;
-}
-
-// The host is about to free or reuse the cost order's buffers: the order stream's kernels end first.
-hipError_t sync_order(rt_ctx* c) {
-    if (!c->order_stream) return hipSuccess;
-    const hipError_t e = hipStreamSynchronize(c->order_stream);
-    if (e == hipSuccess) c->order_pending = false;
-    return e;
-}
-
-// The next accelerated dispatch reads the order the order stream wrote: the context's
-// stream waits for it (a device-side wait, the host does not block).
-hipError_t join_order(rt_ctx* c) {
-    if (!c->order_pending) return hipSuccess;
-    c->order_pending = false;
-    return hipStreamWaitEvent(c->stream, c->order_done, 0);
 }
 
 // Records the anim_copied event of the last k_refit's slot if it is still pending.
@@ -4164,43 +4074,18 @@ int flush_updates(rt_ctx* c, bool grow = false) {
                               c->accel.origin_lim, c->accel.mt ? 1 : 0,
                               {c->accel.mt_z[0], c->accel.mt_z[1], c->accel.mt_z[2]},
                               acc ? c->prim_idx_dev : nullptr, c->cone_cull};
-            if (!c->refit_ctr) {
-                const size_t words = kRefitFlag0 + 16 * kRefitFlags;  // tickets, done, then the flags
-                if (hipMalloc(&c->refit_ctr, words * sizeof(unsigned)) != hipSuccess) return RT_ERR_NO_MEMORY;
-                HIP_TRY(hipMemsetAsync(c->refit_ctr, 0, words * sizeof(unsigned), c->stream));
-                c->ctr_tickets = c->ctr_done = 0;
-            }
-            // mode 4: the records copied to the device first, then read there by every role
-            // (direct, one launch): one crossing of the host link instead of one per reader
-            const char* src = pin_dev;
             const int mode = c->refit_mode >= 0 ? c->refit_mode : c->direct_reads <= kDirectReads ? 2 : 1;
-            if (mode == 4) {
-                if (c->refit_dev_cap < bytes) {
-                    hipFree(c->refit_dev);
-                    c->refit_dev = nullptr;
-                    c->refit_dev_cap = 0;
-                    if (hipMalloc(&c->refit_dev, bytes) != hipSuccess) return RT_ERR_NO_MEMORY;
-                    c->refit_dev_cap = bytes;
-                }
-                HIP_TRY(hipMemcpyAsync(c->refit_dev, pin, bytes, hipMemcpyHostToDevice, c->stream));
-                src = c->refit_dev;
-            }
-            const int waves = mode == 2 ? 1 : kRefitWaves;  // per workgroup of a single launch
             RefitArgs r{};
-            r.fresh = reinterpret_cast<const FlatShape*>(src);
-            r.flags = reinterpret_cast<const int*>(src + n * sizeof(FlatShape));
-            r.gbox = gbox ? reinterpret_cast<const float4*>(src + box_at) : nullptr;
-            r.nsrc = nodes ? reinterpret_cast<const FlatNode*>(src + rec_bytes) : nullptr;
+            r.fresh = reinterpret_cast<const FlatShape*>(pin_dev);
+            r.flags = reinterpret_cast<const int*>(pin_dev + n * sizeof(FlatShape));
+            r.gbox = gbox ? reinterpret_cast<const float4*>(pin_dev + box_at) : nullptr;
+            r.nsrc = nodes ? reinterpret_cast<const FlatNode*>(pin_dev + rec_bytes) : nullptr;
             r.report = reinterpret_cast<int*>(const_cast<char*>(pin_dev) + c->report_at[slot]);
-            r.ctr = c->refit_ctr;
-            r.tbase = c->ctr_tickets;
-            r.abase = c->ctr_done;
-            const int per = 64 * (mode == 1 ? 1 : waves);  // record / node-set lanes per workgroup
-            r.na = (n + per - 1) / per;
+            r.na = (n + 63) / 64;  // the record and node-set roles always run in one-wave workgroups
             r.N = c->N;
             r.n_items = nodes && acc ? c->n_titems : 0;
             r.titem_ref = c->titem_ref;
-            r.nd = nodes ? (c->N + r.n_items + per - 1) / per : 0;
+            r.nd = nodes ? (c->N + r.n_items + 63) / 64 : 0;
             r.nb = n > 0 ? c->anim.nodes : 0;
             r.dirty = c->refit_dirty;
             r.n_big = c->n_big;
@@ -4208,8 +4093,7 @@ int flush_updates(rt_ctx* c, bool grow = false) {
             r.dlist = c->refit_list;
             r.n_dirty = n > 0 && acc ? c->n_dirty : 0;
             r.rec = c->accel.mt ? kWideRecMt : kWideRec;
-            r.wait = mode == 0 ? 1 : mode == 3 ? 2 : 0;
-            r.direct = mode == 2 || mode == 4;
+            r.direct = mode == 2;
             // waves per workgroup: the node and slot roles' own launch takes kRefitWaves (a
             // slot's or node's list in one step), a launch with the one-wave roles one
             auto go = [&](const RefitArgs& ra, int waves) -> int {
@@ -4218,8 +4102,6 @@ int flush_updates(rt_ctx* c, bool grow = false) {
                 if (grid == 0) return RT_OK;
                 hipLaunchKernelGGL(k_refit, dim3(grid), dim3(64 * waves), 0, c->stream, c->anim, out, ra);
                 HIP_TRY(hipGetLastError());
-                if (ra.wait == 1) c->ctr_tickets += static_cast<unsigned>(grid);
-                if (ra.wait) c->ctr_done += static_cast<unsigned>(ra.na);
                 return RT_OK;
             };
             if (mode == 1) {  // records and node sets, then (a kernel boundary later) the boxes
@@ -4227,7 +4109,7 @@ int flush_updates(rt_ctx* c, bool grow = false) {
                 r1.nb = r1.n_dirty = 0;
                 r2.na = r2.nd = 0;
                 if ((rc = go(r1, 1)) != RT_OK || (rc = go(r2, kRefitWaves)) != RT_OK) return rc;
-            } else if ((rc = go(r, waves)) != RT_OK) {
+            } else if ((rc = go(r, 1)) != RT_OK) {
                 return rc;
             }
             lap("records staged, k_refit launched");
@@ -4363,7 +4245,6 @@ void inherit(rt_ctx* b, const rt_ctx* c) {
     b->moving_period = c->moving_period;
     b->moving_dilate = c->moving_dilate;
     b->moving_split = c->moving_split;
-    b->order_mode = c->order_mode;
     b->frame_event = c->frame_event;
     b->refit_mode = c->refit_mode;
     b->tail_from = c->tail_from;
@@ -4541,7 +4422,6 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
         hipLaunchKernelGGL(k_lane<false>, grid, dim3(kBlock), lds, c->stream, c->geo_leaf, c->geo_lin, c->mat,
                            c->nodes, kp);
     } else if (kind == RT_KERNEL_ACCEL) {
-        HIP_TRY(join_order(c));  // the previous cost frame's order, if it ran on the order stream
         KParams k2 = kp;
         k2.tiles_x = (kp.width + 7) / 8;
         k2.tiles = k2.tiles_x * ((kp.out_rows + 7) / 8);
@@ -4572,7 +4452,6 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
             k2.tile_order = c->tile_order;
         } else if (c->schedule != RT_SCHED_ROWS) {
             if (c->sched_cap < k2.tiles) {
-                HIP_TRY(sync_order(c));
                 hipFree(c->sched_cost);
                 hipFree(c->sched_order);
                 hipFree(c->sched_sets);
@@ -4823,10 +4702,7 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
             unsigned* next = c->sched_sets + (1 - c->sched_parity) * sched_set_words(c->sched_cap);
             const int groups = (k2.tiles + kOrderThreads - 1) / kOrderThreads;
             const unsigned* cost = c->sched_cost;
-            // the order stream (rt_debug_order_stream): behind the render's end, off the frame's end
-            const bool side = c->order_mode == 2 || (c->order_mode == 1 && latency);
-            hipStream_t os = c->stream;
-            if (!side && latency && c->frame_event) {
+            if (latency && c->frame_event) {
                 // a waited frame ends here (rt_sync_frame); the order runs behind it on the same
                 // stream, within the host's turnaround to the next dispatch
                 if (!c->frame_ev && hipEventCreateWithFlags(&c->frame_ev, hipEventDisableTiming) != hipSuccess)
@@ -4834,40 +4710,24 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
                 HIP_TRY(hipEventRecord(c->frame_ev, c->stream));
                 c->frame_ev_set = true;
             }
-            if (side) {
-                if (!c->order_stream) {
-                    if (rtx::make_stream(&c->order_stream, false) != hipSuccess ||
-                        hipEventCreateWithFlags(&c->order_ready, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&c->order_done, hipEventDisableTiming) != hipSuccess)
-                        return RT_ERR_DEVICE;
-                }
-                HIP_TRY(hipEventRecord(c->order_ready, c->stream));
-                HIP_TRY(hipStreamWaitEvent(c->order_stream, c->order_ready, 0));
-                os = c->order_stream;
-            }
             if (dilate > 0) {
                 const size_t need = static_cast<size_t>(k2.tiles) + static_cast<size_t>(groups) * kOrderBuckets;
                 if (c->dil_cap < need) {
-                    HIP_TRY(sync_order(c));
                     hipFree(c->dil_cost);
                     c->dil_cost = nullptr;
                     c->dil_cap = 0;
                     if (hipMalloc(&c->dil_cost, need * sizeof(unsigned)) != hipSuccess) return RT_ERR_NO_MEMORY;
                     c->dil_cap = need;
                 }
-                hipLaunchKernelGGL(k_cost_dilate, dim3(groups), dim3(kOrderThreads), 0, os, c->sched_cost,
+                hipLaunchKernelGGL(k_cost_dilate, dim3(groups), dim3(kOrderThreads), 0, c->stream, c->sched_cost,
                                    k2.tiles, k2.tiles_x, dilate, c->dil_cost, c->dil_cost + k2.tiles);
                 cost = c->dil_cost;
                 set = c->dil_cost + k2.tiles;
             }
             hipLaunchKernelGGL(k_tile_order, dim3(groups), dim3(kOrderThreads),
-                               0, os, cost, k2.tiles, set, next,
+                               0, c->stream, cost, k2.tiles, set, next,
                                static_cast<int>(sched_set_words(c->sched_cap)), c->sched_order,
                                c->schedule == RT_SCHED_COST_XCD ? 1 : 0);
-            if (side) {
-                HIP_TRY(hipEventRecord(c->order_done, os));
-                c->order_pending = true;
-            }
             c->sched_parity = 1 - c->sched_parity;
             c->sched_valid = k2.tiles;
         }
@@ -5050,8 +4910,6 @@ int rt_destroy(rt_ctx* c) {
     hipFree(c->sched_sets);
     hipFree(c->anim_maps);
     hipFree(c->anim_sbox);
-    hipFree(c->refit_ctr);
-    hipFree(c->refit_dev);
     for (int k = 0; k < rt_ctx::kAnimRing; ++k) {
         if (c->anim_pinned[k]) hipHostFree(c->anim_pinned[k]);
         if (c->anim_copied[k]) hipEventDestroy(c->anim_copied[k]);
@@ -5060,9 +4918,6 @@ int rt_destroy(rt_ctx* c) {
     for (hipEvent_t e : c->ring1) if (e) hipEventDestroy(e);
     if (c->sync_ev) hipEventDestroy(c->sync_ev);
     if (c->frame_ev) hipEventDestroy(c->frame_ev);
-    if (c->order_ready) hipEventDestroy(c->order_ready);
-    if (c->order_done) hipEventDestroy(c->order_done);
-    if (c->order_stream) hipStreamDestroy(c->order_stream);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -5645,7 +5500,7 @@ extern "C" int rt_debug_refit_stats(rt_ctx* c, long long* out) {
 }
 
 extern "C" int rt_debug_refit(rt_ctx* c, int mode) {
-    if (!c || mode < -1 || mode > 4) return RT_ERR_INVALID;
+    if (!c || (mode != -1 && mode != 1 && mode != 2)) return RT_ERR_INVALID;
     c->refit_mode = mode;
     return RT_OK;
 }
@@ -5706,14 +5561,6 @@ extern "C" int rt_debug_moving(rt_ctx* c, int period, int dilate, int split) {
     c->moving_period = period;
     c->moving_dilate = dilate;
     c->moving_split = split ? 1 : 0;
-    return RT_OK;
-}
-
-// Diagnostics / policy: where the cost order's kernels run (0: the context's stream after
-// the render; 1: an order stream in latency-mode dispatches; 2: the order stream always).
-extern "C" int rt_debug_order_stream(rt_ctx* c, int mode) {
-    if (!c || mode < 0 || mode > 2) return RT_ERR_INVALID;
-    c->order_mode = mode;
     return RT_OK;
 }
 

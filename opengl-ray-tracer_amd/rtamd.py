@@ -760,9 +760,10 @@ class ComputeShader:
         return int(fn(self._h))
 
     def debug_refit(self, mode):
-        """rt_debug_refit: 0 one launch (box roles wait, by tickets), 1 two launches, 2 one launch
-        (direct), 3 one launch (box roles wait, in start order), 4 as 2 from a device copy;
-        -1 (the default) 2 for few records, else 1."""
+        """rt_debug_refit: 1 two launches (records, then boxes), 2 one launch whose box roles
+        read the records themselves; -1 (the default) 2 for few records, else 1. Anything else is
+        refused: the one-launch shapes with device-side waits and the device copy of the records
+        measured slower (profiles/r05x_refit_record_probe.txt, r06_anim_probe_modes.txt)."""
         fn = self._lib.rt_debug_refit
         fn.argtypes = [_P, _I]
         fn.restype = _I
@@ -814,13 +815,6 @@ class ComputeShader:
         fn = self._lib.rt_debug_moving
         fn.argtypes = [_P, _I, _I, _I]
         self._chk(fn(self._h, int(period), int(dilate), int(split)), "rt_debug_moving")
-
-    def debug_order_stream(self, mode):
-        """Where the cost order's kernels run: 0 the context's stream after the render,
-        1 an order stream in latency-mode dispatches, 2 the order stream always."""
-        fn = self._lib.rt_debug_order_stream
-        fn.argtypes = [_P, _I]
-        self._chk(fn(self._h, int(mode)), "rt_debug_order_stream")
 
     def debug_frame_event(self, on):
         """Latency-mode cost frames record the event rt_sync_frame waits for (1) or not (0)."""

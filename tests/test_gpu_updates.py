@@ -294,11 +294,10 @@ def test_animated_mt_and_brute_frames_refit(ctx, fresh, mode):
         same(ctx.render(W, H), fresh.render(W, H), f"{mode} reference upload {k}")
 
 
-@pytest.mark.parametrize("refit", [-1, 0, 1, 2, 3, 4])
+@pytest.mark.parametrize("refit", [-1, 1, 2])
 def test_refit_launch_modes_equal_fresh_upload(ctx, fresh, refit):
-    """Every launch shape of k_refit (rt_debug_refit: 0 one launch ordered by tickets,
-    1 two launches, 2 one launch reading the records itself, 3 one launch in start
-    order, 4 as 2 from a device copy of the records; -1, the default, picks 1 or 2)
+    """Every launch shape of k_refit (rt_debug_refit: 1 two launches, 2 one launch
+    reading the records itself; -1, the default, picks 1 or 2)
     refits the car's turning wheels to the frames of a fresh
     upload, bit for bit, barycentric (back-face cones recomputed) and Moller-Trumbore."""
     W, H = 192, 108
@@ -323,6 +322,39 @@ def test_refit_launch_modes_equal_fresh_upload(ctx, fresh, refit):
                 fresh.set_kernel(rtamd.KERNEL_AUTO)
                 same(ctx.render(W, H), fresh.render(W, H), f"refit {refit} mt {mt} frame {k}")
             assert ctx.debug_anim_rebuilds() == r0
+    finally:
+        ctx.debug_refit(-1)
+        ctx.set_animated(np.zeros(0, np.int32))
+
+
+def test_refit_mode_rejects_removed_shapes(ctx, fresh):
+    """rt_debug_refit accepts -1, 1 and 2 only. The removed launch shapes (0, 3, 4) and
+    values out of range answer the invalid-argument status and leave the mode as it was:
+    an animated frame after them still equals the fresh upload."""
+    W, H = 192, 108
+    fs = rtamd.generate(3, 0, W, H)
+    ids, frames = bench.wheel_frames(fs, 6)
+    try:
+        ctx.upload(fs)
+        ctx.debug_refit(2)
+        for bad in (0, 3, 4, 5, -2):
+            with pytest.raises(rtamd.RTError) as e:
+                ctx.debug_refit(bad)
+            assert e.value.code == -1, bad  # RT_ERR_INVALID
+        ctx.set_params(W, H, 3, True, False, False)
+        ctx.set_kernel(rtamd.KERNEL_AUTO)
+        ctx.set_animated(ids)
+        ctx.render(W, H)
+        r0 = ctx.debug_anim_rebuilds()
+        ctx.animate(frames[0])
+        host = rtamd.FlatScene(fs.shapes.copy(), fs.nodes.copy(), fs.indices, fs.camera, fs.light)
+        host.shapes[ids] = frames[0]
+        oracle.update_bvh(host, ids)
+        fresh.upload(host)
+        fresh.set_params(W, H, 3, True, False, False)
+        fresh.set_kernel(rtamd.KERNEL_AUTO)
+        same(ctx.render(W, H), fresh.render(W, H), "animated frame after the refused modes")
+        assert ctx.debug_anim_rebuilds() == r0
     finally:
         ctx.debug_refit(-1)
         ctx.set_animated(np.zeros(0, np.int32))

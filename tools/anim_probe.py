@@ -25,7 +25,7 @@ def main():
     ap.add_argument("--upload", default="device", choices=["device", "reference", "static"])
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--latency", type=int, default=1)
-    ap.add_argument("--refit", type=int, default=-1, help="rt_debug_refit mode (-1: default)")
+    ap.add_argument("--refit", type=int, default=-1, help="rt_debug_refit launch shape: 1 two launches, 2 one direct launch (-1: the library's choice)")
     a = ap.parse_args()
     import torch
     import bench
