@@ -257,9 +257,19 @@ __global__ __launch_bounds__(kThreads) void k_lbvh_leaves(const unsigned long lo
     leaf.numShapes = 1;
     if (n == 1) return;
     // Bottom-up unions: the second arrival at a node has both children's boxes.
+    // The box this thread wrote last must be in memory before its arrival counts: the
+    // other child's thread may run on another XCD, behind another L2. An acq_rel
+    // fetch_add alone compiled to the L2 write-back and the atomic back to back, with no
+    // wait for the boundsMax store of the iteration before or for the write-back itself
+    // (the loop's back edge lost the release's s_waitcnt), and a 100k-triangle build now
+    // and then left an inner boundsMax that was not the union of its children. So the
+    // release is spelled out, with an explicit wait that the compiler keeps.
     int p = parent[j];
     while (p >= 0) {
-        if (__hip_atomic_fetch_add(&arrivals[p], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) expcnt(0) lgkmcnt(0): stores and write-back done
+        if (__hip_atomic_fetch_add(&arrivals[p], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         FlatNode& nd = nodes[p];
         const FlatNode& a = nodes[nd.leftChild];
         const FlatNode& b = nodes[nd.rightChild];

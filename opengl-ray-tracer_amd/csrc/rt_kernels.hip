@@ -5634,6 +5634,19 @@ extern "C" int rt_debug_sched_order(rt_ctx* c, int* out, int n) {
     return c->sched_order ? k : 0;
 }
 
+// Diagnostics: the tile costs that order was made from, as the last cost-recording
+// dispatch wrote them (raw: not the dilated copy of rt_debug_cost_dilate), into
+// out[0, n); returns the tiles copied (0 when no order exists yet).
+extern "C" int rt_debug_sched_cost(rt_ctx* c, unsigned* out, int n) {
+    if (!c || n < 0 || (n > 0 && !out)) return RT_ERR_INVALID;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    HIP_TRY(sync_stream(c));
+    const int k = std::min(n, c->sched_valid);
+    if (k > 0 && c->sched_cost)
+        HIP_TRY(hipMemcpy(out, c->sched_cost, static_cast<size_t>(k) * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return c->sched_cost ? k : 0;
+}
+
 // Diagnostics: the first k tiles of the cost order (the heaviest) each run as `parts`
 // waves (1, 2, 4 or 8), one band of 64 / parts pixels per wave; parts = 1: off;
 // k = -1: the default policy (kHeavyAutoSlots).

@@ -799,6 +799,17 @@ class ComputeShader:
             raise RTError("rt_debug_sched_order", k)
         return buf[:k].copy()
 
+    def debug_sched_cost(self, n):
+        """The first n tiles' costs as the last cost-recording dispatch wrote them (raw, not
+        dilated): what the current cost order was made from; empty before one exists."""
+        fn = self._lib.rt_debug_sched_cost
+        fn.argtypes = [_P, _P, _I]
+        buf = np.zeros(max(n, 1), np.uint32)
+        k = fn(self._h, _ptr(buf), int(n))
+        if k < 0:
+            raise RTError("rt_debug_sched_cost", k)
+        return buf[:k].copy()
+
     def debug_refit_stats(self):
         """The refit's shape: dirty slots, largest / total prim range, nodes, entries."""
         fn = self._lib.rt_debug_refit_stats

@@ -3,13 +3,15 @@
 The LBVH is not the reference builder's tree, so the parity target is the
 oracle rendering the SAME tree (read back through the C ABI): the frame the
 reference shader would produce if its host had uploaded that tree. The tree
-itself is checked structurally and its boxes against the oracle's restated
-updateBVH (growToInclude of each shape into every node that lists it).
+itself is checked structurally, its boxes against the oracle's restated
+updateBVH (growToInclude of each shape into every node that lists it), and node
+for node against the plain restatement of the whole build (tests/lbvh_ref.py).
 """
 import numpy as np
 import pytest
 import torch
 
+import lbvh_ref
 import oracle
 import rtamd
 from test_gpu_parity import CFG_BOUNCES, TOL, _soup, check, gpu_rows
@@ -79,6 +81,28 @@ def test_lbvh_boxes_are_reference_bounding_boxes(ctx):
     oracle.update_bvh(grown, np.arange(len(fs2.shapes), dtype=np.int32))
     assert np.array_equal(grown.nodes["boundsMin"], fs2.nodes["boundsMin"])
     assert np.array_equal(grown.nodes["boundsMax"], fs2.nodes["boundsMax"])
+
+
+@pytest.mark.parametrize("name", sorted(lbvh_ref.SCENES))
+def test_lbvh_equals_the_plain_reference(ctx, name):
+    """The device build is the LBVH of its shapes, node for node: the sort order, every
+    node's children and key range, and every box equal tests/lbvh_ref.py's restatement
+    (centres, bounds, Morton codes, keys, the radix tree over the sorted keys). Any valid
+    tree passes check_structure; only this one is the spatially coherent tree the build
+    exists for. Shape counts at the wave and block edges of n and n - 1 with the bounds set
+    in the last partial wave, equal codes (all, in pairs, all but one), a degenerate axis,
+    planes and walls, non-finite records (rt_upload_scene takes them as they are: it checks
+    the tree, not the shapes) and the mesh scenes."""
+    fs = lbvh_ref.scene(name)
+    ctx.upload(fs)
+    ctx.build_lbvh()
+    nodes, indices = ctx.read_tree()
+    rnodes, rindices, _ = ref = lbvh_ref.reference(name)
+    diff = lbvh_ref.first_difference(fs, nodes, indices, ref)
+    assert diff is None, f"{name}: {diff}"
+    assert np.array_equal(indices, rindices)
+    for f in ("leftChild", "rightChild", "startShapeIdx", "numShapes", "boundsMin", "boundsMax"):
+        assert np.array_equal(nodes[f], rnodes[f]), f
 
 
 CASES = [  # cfg, W, H, y0, rows
