@@ -195,6 +195,38 @@ int rt_dispatch_rows_fmt(struct rt_ctx* ctx, int width, int height, int y0, int 
 int rt_dispatch_rows_ex(struct rt_ctx* ctx, int width, int height, int y0, int stripe, int period, int out_rows,
                         float* dst, size_t pitch, int format);
 
+/* Supersampling: every pixel is the mean of n x n samples on the regular sub-pixel grid.
+ * n in {1, 2, 4, 8}; 1 (default) is today's frame. RT_ERR_INVALID for any other n.
+ *
+ * Applied at the next dispatch, and to every dispatch form (rt_dispatch, rt_dispatch_rows,
+ * _fmt, _ex; all three formats, any y0 / stripe / period / out_rows). The caller's width,
+ * height, rows, pitch and rt_params keep their meaning: they describe the OUTPUT frame.
+ * The samples are the pixels of the one-sample frame with width, height, y0, stripe,
+ * period, out_rows, resX and resY all multiplied by n (the reference's pixel NDC is
+ * 2x/resX - 1 and its background y/resY, so that frame's pixels are exactly the n x n
+ * regular sub-pixel grid of this one). The filter is fixed, per channel (alpha included)
+ * in float32: log2 n rounds along x, each a[i] = a[2i] + a[2i+1]; then log2 n such rounds
+ * along y; then one multiply by 1/n^2 (exact). Alpha stays exactly 1. So the frame is that
+ * box filter of the renderer's own n*W x n*H frame, bit for bit, for every kernel variant
+ * and every other setting.
+ *
+ * A dispatch whose sample frame breaks a limit of the one-sample dispatch (more than 65535
+ * rows of 8x8 tiles, width * rows >= 2^32 samples, a scaled value that overflows int) is
+ * refused with RT_ERR_INVALID before anything is launched.
+ *
+ * Frames the accelerated kernel renders (RT_KERNEL_ACCEL in rt_accel_info::last_kernel)
+ * average each n x n block inside the render kernel's store: an 8x8 tile of samples is
+ * one wave, so nothing but the output frame is written. Such frames render without ray
+ * compaction (rt_set_tail is ignored for them), and latency mode splits a heavy tile only
+ * into bands of whole blocks. Every other frame (RT_KERNEL_LANE, RT_KERNEL_PACKET, no
+ * usable accelerator, a far camera) renders the sample frame into a surface the context
+ * keeps between frames and filters it with a second small kernel.
+ *
+ * rt_collect_stats* is not affected: it counts the one-sample frame it is given. A host
+ * that wants the sample frame's ray counts collects them at n*W x n*H with resX, resY
+ * times n. Group frames (rt_group.h) stay one sample per pixel. */
+int rt_set_samples(struct rt_ctx* ctx, int n);
+
 /* glMemoryBarrier + wait: blocks until the context's stream is drained. */
 int rt_sync(struct rt_ctx* ctx);
 

@@ -130,6 +130,10 @@ struct KParams {
                                              // (12 B per pixel), 2 RGBA32F at the image row (RT_FORMAT_RGBA32F_IMAGE)
     float shadow_off;                        // k_accel's shadow-ray offset: 1e-3 (BVH branch, gpu_shader.comp:469);
                                              // 1e-5 when it renders the brute branch (:565, rt_ctx::brute)
+    int ss;                                  // rt_set_samples: 1, or n > 1 when the fields above describe the
+                                             // SAMPLE frame (width, height, y0, stripe, period, out_rows, resX,
+                                             // resY all times n) while dst / pitch / rgb stay the n-times smaller
+                                             // output's. Only the supersampling k_accel instances read it.
 };
 
 // Row mapping of rt_dispatch_rows_ex (include/rt_api.h): stripes of `stripe` rows
@@ -327,6 +331,26 @@ __device__ __forceinline__ void store_px(const KParams& kp, int r, int x, float4
     __builtin_nontemporal_store(v.y, &row[x].y);
     __builtin_nontemporal_store(v.z, &row[x].z);
     __builtin_nontemporal_store(v.w, &row[x].w);
+}
+
+// The supersampling store (rt_set_samples, kp.ss = n > 1): the first lane of an n x n block
+// of sample pixels writes their mean to output row r / n, column x / n (sample row r,
+// column x; image_row of n * R + j is n * the output's image row + j).
+__device__ __forceinline__ void store_px_ss(const KParams& kp, int r, int x, float4 v) {
+    const int sh = 31 - __builtin_clz(kp.ss);
+    if (kp.rgb == 1) {
+        float* p = reinterpret_cast<float*>(kp.dst + static_cast<size_t>(r >> sh) * kp.pitch) + 3 * (x >> sh);
+        __builtin_nontemporal_store(v.x, p);
+        __builtin_nontemporal_store(v.y, p + 1);
+        __builtin_nontemporal_store(v.z, p + 2);
+        return;
+    }
+    const int row_i = (kp.rgb == 2 ? image_row(kp, r) : r) >> sh;
+    float4* px = reinterpret_cast<float4*>(kp.dst + static_cast<size_t>(row_i) * kp.pitch) + (x >> sh);
+    __builtin_nontemporal_store(v.x, &px->x);
+    __builtin_nontemporal_store(v.y, &px->y);
+    __builtin_nontemporal_store(v.z, &px->z);
+    __builtin_nontemporal_store(v.w, &px->w);
 }
 
 }  // namespace rtd

@@ -19,12 +19,16 @@
 //       first occluder closer than the light (equivalent to the reference's
 //       closest-hit test). It renders the frames the accelerator
 //       cannot (accel_usable).
-//   k_accel<TIMED, COST, TAIL, MT, REC, QUEUE> : the production kernel. One 8x8
+//   k_accel<TIMED, COST, TAIL, MT, REC, QUEUE, SS> : the production kernel. One 8x8
 //       tile (or one band of a split heavy tile) per wave over the exact-result
 //       accelerator (accel.h): packet walks (packet_walk) for coherent rays,
 //       per-lane walks with LDS stacks (lane_walk) for the rest, same image as
 //       the kernels above. launch() picks the instance; the one without counters,
-//       queue or records (k_accel<false, false>) renders the plain frames.
+//       queue or records (k_accel<false, false>) renders the plain frames. The SS
+//       instances render supersampled frames (rt_set_samples): the sample frame's
+//       tiles, each n x n block of lanes stored as one mean pixel.
+//   k_box_filter<N> : rt_set_samples for the frames k_accel does not render: the
+//       N x N box filter of a sample frame the kernels above rendered.
 //   k_accel_tail    : the remaining bounces of the rays k_accel queued
 //       (rt_set_tail), 64 rays from one screen region to a wave.
 //   k_tile_order / k_cost_dilate : the next frame's dispatch order from the tile
@@ -1707,7 +1711,9 @@ __device__ __forceinline__ void bounce_step(const AccelPtrs& A, const float4* __
 
 // Walk counts (node steps, tests) are kept when COST: they are the cost that
 // orders a later dispatch (rt_set_schedule). COUNT adds the per-walk records.
-template <bool COUNT, bool COST = true, bool TAIL = false, bool MT = false, bool QUEUE = TAIL>
+// SS: a supersampled frame (rt_set_samples): kp describes the sample frame, and the store
+// writes the mean of each kp.ss x kp.ss block of lanes (store_px_ss) instead of every lane.
+template <bool COUNT, bool COST = true, bool TAIL = false, bool MT = false, bool QUEUE = TAIL, bool SS = false>
 __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, const KParams& kp, int tile,
                            int part, int* stk, unsigned short* stt, int cap, WalkCount& wc,
                            unsigned long long* rec, bool heavy) {
@@ -1777,6 +1783,22 @@ __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, c
         }
     }
     const PixelCoord pc = tile_pixel(kp, tile);
+    if (SS) {
+        // The box filter of rt_set_samples (include/rt_api.h), in its fixed order: an xor
+        // butterfly over the lane bits of x (0..2), then of y (3..5), log2 n rounds each, so
+        // every lane of an n x n block ends with the block's sum (addition commutes: the same
+        // bits in each). Lanes outside the frame or not of this band hold zeros, and a block
+        // lies wholly inside or outside both (launch() splits only into bands of whole blocks).
+        for (int b = 1; b < kp.ss; b <<= 1)
+            acc = acc + mk(__shfl_xor(acc.x, b), __shfl_xor(acc.y, b), __shfl_xor(acc.z, b));
+        for (int b = 8; b < 8 * kp.ss; b <<= 1)
+            acc = acc + mk(__shfl_xor(acc.x, b), __shfl_xor(acc.y, b), __shfl_xor(acc.z, b));
+        const int lane = threadIdx.x & 63;
+        const float w = 1.0f / static_cast<float>(kp.ss * kp.ss);  // a power of two: exact
+        if (pc.active && mine && ((lane | lane >> 3) & (kp.ss - 1)) == 0)
+            store_px_ss(kp, pc.r, pc.x, make_float4(acc.x * w, acc.y * w, acc.z * w, 1.0f));
+        return;
+    }
     if (pc.active && mine && !deferred) store_px(kp, pc.r, pc.x, make_float4(acc.x, acc.y, acc.z, 1.0f));
 }
 
@@ -1790,7 +1812,10 @@ __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, c
 // dispatch records each tile's cost for the next order (rt_set_schedule); without COST
 // it can only record the wall-time cost (kp.cost_time), which needs no counters.
 // TAIL: queue the rays alive after bounce tail_from - 1 for k_accel_tail (rt_set_tail).
-template <bool TIMED, bool COST = true, bool TAIL = false, bool MT = false, bool REC = COST, bool QUEUE = TAIL>
+// SS: the supersampling instances (rt_set_samples): the same tiles over the sample frame,
+// each n x n block of lanes stored as one mean pixel (accel_tile).
+template <bool TIMED, bool COST = true, bool TAIL = false, bool MT = false, bool REC = COST, bool QUEUE = TAIL,
+          bool SS = false>
 __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, const float4* __restrict__ mat, KParams kp) {
     extern __shared__ int lds_stack[];
     // per-lane stacks, entry j of lane i at [j * blockDim.x + i]: codes, then bf16 entry parameters
@@ -1823,8 +1848,8 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, con
         // a split tile's parts stamp records tiles + slot (rt_debug_tile_times with room for them)
         unsigned long long* rec =
             TIMED ? kp.tile_times + kTileRec * static_cast<size_t>(part > 0 ? kp.tiles + slot : tile) : nullptr;
-        accel_tile<TIMED, COST, TAIL, MT, QUEUE>(A, mat, kp, tile, part, stk, stt, kp.lane_stack, wc, rec,
-                                                 slot < kp.lane_k);
+        accel_tile<TIMED, COST, TAIL, MT, QUEUE, SS>(A, mat, kp, tile, part, stk, stt, kp.lane_stack, wc, rec,
+                                                     slot < kp.lane_k);
         if (TIMED) {
             const unsigned long long t1 = wall_clock64();
             unsigned long long sn = wc.nodes, st = wc.tests, mn = wc.nodes, mt = wc.tests;
@@ -1959,6 +1984,54 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel_tail(AccelPtrs A
     }
     if (blockIdx.x == 0)
         for (int b = threadIdx.x; b < kp.tail_counters; b += blockDim.x) kp.tail_count_next[b] = 0;
+}
+
+// The general path of rt_set_samples: the sample frame was rendered by any kernel into a
+// scratch surface (compact rows, RGBA32F); one thread per output pixel applies the box
+// filter in the order rt_api.h fixes -- log2 N pairwise rounds along x, then along y,
+// i.e. balanced trees over contiguous halves, then one multiply -- per channel, alpha
+// included, and writes the output in the requested format and row mapping.
+template <int N>
+__device__ __forceinline__ float4 box_x(const float4* __restrict__ p) {
+    if constexpr (N == 1) {
+        return p[0];
+    } else {
+        const float4 a = box_x<N / 2>(p), b = box_x<N / 2>(p + N / 2);
+        return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    }
+}
+template <int N, int M>
+__device__ __forceinline__ float4 box_y(const char* __restrict__ p, size_t pitch) {
+    if constexpr (M == 1) {
+        return box_x<N>(reinterpret_cast<const float4*>(p));
+    } else {
+        const float4 a = box_y<N, M / 2>(p, pitch), b = box_y<N, M / 2>(p + (M / 2) * pitch, pitch);
+        return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    }
+}
+// width, height, y0, stripe, period, out_rows: the OUTPUT frame's (rt_dispatch_rows_ex).
+template <int N>
+__global__ __launch_bounds__(256) void k_box_filter(const char* __restrict__ src, size_t src_pitch,
+                                                    char* __restrict__ dst, size_t pitch, int width, int height,
+                                                    int y0, int stripe, int period, int out_rows, int format) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int r = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= width || r >= out_rows) return;
+    const int y = y0 + r + (r / stripe) * (period - stripe);
+    if (y >= height) return;  // not rendered: left untouched, as the one-sample dispatch leaves it
+    float4 v = box_y<N, N>(src + static_cast<size_t>(r) * N * src_pitch + static_cast<size_t>(x) * N * sizeof(float4),
+                           src_pitch);
+    const float w = 1.0f / static_cast<float>(N * N);
+    v = make_float4(v.x * w, v.y * w, v.z * w, v.w * w);
+    if (format == RT_FORMAT_RGB32F) {
+        float* p = reinterpret_cast<float*>(dst + static_cast<size_t>(r) * pitch) + 3 * x;
+        p[0] = v.x;
+        p[1] = v.y;
+        p[2] = v.z;
+        return;
+    }
+    const int row = format == RT_FORMAT_RGBA32F_IMAGE ? y : r;
+    reinterpret_cast<float4*>(dst + static_cast<size_t>(row) * pitch)[x] = v;
 }
 
 __global__ void k_pack_prims(const float4* __restrict__ geo_lin, const int* __restrict__ prim_shape,
@@ -2795,6 +2868,14 @@ struct rt_ctx {
     float* img = nullptr;
     size_t img_pitch = 0;
     int img_w = 0, img_h = 0;
+    // rt_set_samples: n x n samples per pixel. Frames k_accel renders reduce them in its
+    // store (the SS instances); every other frame renders the sample frame into ss_buf
+    // (compact rows, RGBA32F; kept between frames, reallocated when the size changes) and
+    // k_box_filter writes the output. ss_general: rt_debug_ss_general forces the latter.
+    int samples = 1;
+    bool ss_general = false;
+    char* ss_buf = nullptr;
+    size_t ss_bytes = 0;
     unsigned long long* stats_dev = nullptr;
     int cu_count = 256;
     int lane_from_depth = -1;  // bounces >= this use the per-lane walk (0: all, large: none;
@@ -4153,13 +4234,15 @@ size_t sched_set_words(int tiles) {
     return static_cast<size_t>((tiles + kOrderThreads - 1) / kOrderThreads) * kOrderBuckets;
 }
 
+// ss > 1 (rt_set_samples): width .. out_rows are the SAMPLE frame's, ss times the output
+// frame's that dst, pitch and format describe (KParams::ss); resX, resY are scaled to match.
 int fill_kparams(rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows, float* dst,
-                 size_t pitch, KParams& kp, int format = RT_FORMAT_RGBA32F) {
+                 size_t pitch, KParams& kp, int format = RT_FORMAT_RGBA32F, int ss = 1) {
     if (!c->have_scene || !c->have_cam || !c->have_light) return RT_ERR_NO_SCENE;
     const size_t px = format == RT_FORMAT_RGB32F ? 12 : 16, align = format == RT_FORMAT_RGB32F ? 4 : 16;
     if (width <= 0 || height <= 0 || stripe <= 0 || period < stripe || out_rows < 0 || y0 < 0 || !dst ||
         (format != RT_FORMAT_RGBA32F && format != RT_FORMAT_RGB32F && format != RT_FORMAT_RGBA32F_IMAGE) ||
-        pitch < static_cast<size_t>(width) * px ||
+        ss < 1 || pitch < static_cast<size_t>(width / ss) * px ||
         (pitch % align) != 0 || (reinterpret_cast<uintptr_t>(dst) % align) != 0)
         return RT_ERR_INVALID;
     std::memset(&kp, 0, sizeof kp);
@@ -4182,8 +4265,9 @@ int fill_kparams(rt_ctx* c, int width, int height, int y0, int stripe, int perio
     kp.plane_w = h * cam.aspectRatio;
     kp.light_pos = V{c->light.position.x, c->light.position.y, c->light.position.z};
     kp.light_color = V{c->light.color.x, c->light.color.y, c->light.color.z};
-    kp.resX = c->params.resX;
-    kp.resY = c->params.resY;
+    kp.resX = c->params.resX * static_cast<float>(ss);  // a power of two: exact
+    kp.resY = c->params.resY * static_cast<float>(ss);
+    kp.ss = ss;
     kp.maxBounces = c->params.maxBounces;
     kp.useBVH = c->params.useBVH;
     kp.useFresnel = c->params.useFresnel;
@@ -4253,6 +4337,7 @@ void inherit(rt_ctx* b, const rt_ctx* c) {
     b->tree_mode = c->tree_mode;
     b->scene_stack = c->scene_stack;
     b->lane_stack_override = c->lane_stack_override;
+    b->ss_general = c->ss_general;
 }
 
 // The walk policy in force (rt_set_walk, or auto): barycentric frames walk camera
@@ -4360,7 +4445,7 @@ int render_frame(rt_ctx* c, const KParams& kp, rt_ctx** from) {
         KParams kn;
         const int rc = fill_kparams(nxt, kt.width, kt.height, kt.y0, kt.stripe, kt.period, kt.out_rows,
                                     reinterpret_cast<float*>(kt.dst), kt.pitch, kn,
-                                    kt.rgb);
+                                    kt.rgb, kt.ss);
         if (rc != RT_OK) return rc;
         kn.shadow_off = off;
         t = nxt;
@@ -4396,16 +4481,49 @@ int render_frame(rt_ctx* c, const KParams& kp, rt_ctx** from) {
     return RT_OK;
 }
 
-int launch(rt_ctx* c, const KParams& kp, bool stats) {
+// The output-side launch of k_box_filter for a sample frame rendered into c->ss_buf
+// (`out`: the dispatch's own KParams, `out.ss` = n; rt_ctx::samples).
+void launch_box_filter(rt_ctx* c, const KParams& out) {
+    const int n = out.ss, w = out.width / n, rows = out.out_rows / n;
+    auto kfn = n == 2 ? k_box_filter<2> : n == 4 ? k_box_filter<4> : k_box_filter<8>;
+    hipLaunchKernelGGL(kfn, dim3((w + 63) / 64, (rows + 3) / 4), dim3(256), 0, c->stream, c->ss_buf,
+                       static_cast<size_t>(out.width) * sizeof(float4), out.dst, out.pitch, w, out.height / n,
+                       out.y0 / n, out.stripe / n, out.period / n, rows, out.rgb);
+}
+
+int launch(rt_ctx* c, const KParams& kin, bool stats) {
     c->frame_ev_set = false;
     if (const int rc = flush_updates(c)) return rc;  // rt_update_shapes / rt_update_nodes since the last dispatch
-    if (kp.out_rows == 0) return RT_OK;
-    dim3 grid((kp.width + kTileW - 1) / kTileW, (kp.out_rows + kTileH - 1) / kTileH);
+    if (kin.out_rows == 0) return RT_OK;
+    dim3 grid((kin.width + kTileW - 1) / kTileW, (kin.out_rows + kTileH - 1) / kTileH);
     if (grid.y > 65535u) return RT_ERR_INVALID;
     int kind = c->kernel;
-    const bool usable = accel_usable(c, kp);
+    const bool usable = accel_usable(c, kin);
     if (kind == RT_KERNEL_AUTO) kind = usable ? RT_KERNEL_ACCEL : RT_KERNEL_PACKET;
     if (kind == RT_KERNEL_ACCEL && !usable) kind = RT_KERNEL_PACKET;  // same image either way
+    // rt_set_samples: k_accel reduces the samples in its store (the SS instances, fused);
+    // every other frame -- the lane and packet kernels, per-tile records (their instance has
+    // no SS form), rt_debug_ss_general -- is the one-sample render of the sample frame into
+    // the context's scratch surface, then k_box_filter (general).
+    const bool ss = !stats && kin.ss > 1;
+    const bool ss_fused = ss && kind == RT_KERNEL_ACCEL && !c->tile_times && !c->ss_general;
+    KParams kp = kin;
+    if (ss && !ss_fused) {
+        const size_t spitch = static_cast<size_t>(kin.width) * sizeof(float4);
+        const size_t need = spitch * static_cast<size_t>(kin.out_rows);
+        if (need != c->ss_bytes) {
+            HIP_TRY(sync_stream(c));
+            hipFree(c->ss_buf);
+            c->ss_buf = nullptr;
+            c->ss_bytes = 0;
+            if (hipMalloc(&c->ss_buf, need) != hipSuccess) return RT_ERR_NO_MEMORY;
+            c->ss_bytes = need;
+        }
+        kp.dst = c->ss_buf;
+        kp.pitch = spitch;
+        kp.rgb = RT_FORMAT_RGBA32F;
+        kp.ss = 1;
+    }
     const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
     const bool rec = !stats && c->timing;  // rt_set_kernel_timing
     hipEvent_t e0 = c->ev0, e1 = c->ev1;
@@ -4421,6 +4539,7 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
     } else if (kind == RT_KERNEL_LANE) {
         hipLaunchKernelGGL(k_lane<false>, grid, dim3(kBlock), lds, c->stream, c->geo_leaf, c->geo_lin, c->mat,
                            c->nodes, kp);
+        if (ss) launch_box_filter(c, kin);
     } else if (kind == RT_KERNEL_ACCEL) {
         KParams k2 = kp;
         k2.tiles_x = (kp.width + 7) / 8;
@@ -4583,7 +4702,10 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
             // (config 2, the MT car; r04zz profiles), and in flight the ranking matters less.
             const bool whole = k2.tile_cost && c->cost_time != 0 && !c->tile_times && latency &&
                                !(c->moving && c->moving_split);
-            if (stamps_fit && hp > 1 && hk > 0 && !whole) {
+            // a supersampled frame's bands hold whole n x n blocks of lanes (8 / hp rows >= n),
+            // or the tile is not split: its store reduces each block within one wave
+            const bool blocks_whole = !ss_fused || hp * k2.ss <= 8;
+            if (stamps_fit && hp > 1 && hk > 0 && !whole && blocks_whole) {
                 k2.heavy_k = std::min(hk, k2.tiles);
                 k2.heavy_parts = hp;
             }
@@ -4619,7 +4741,9 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
                                   : (c->accel.st.item_ref.size() >= kTailAutoItems ? 2 : 0);
         // the queue's pixel word is row * width + x in 32 bits (rt_device.h): larger
         // frames render without compaction
-        const bool tail = tail_from > 0 && tail_from < k2.maxBounces &&
+        // Supersampled frames render without it too: k_accel_tail finishes pixels one ray
+        // at a time and cannot take part in the block reduction (same image either way)
+        const bool tail = tail_from > 0 && tail_from < k2.maxBounces && !ss_fused &&
                           static_cast<unsigned long long>(k2.width) * k2.out_rows < (1ull << 32);
         const int rx = (k2.tiles_x + 7) / 8, regions = rx * ((k2.tiles / k2.tiles_x + 7) / 8);
         if (tail) {
@@ -4683,6 +4807,21 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
         } else if (k2.cost_time) {
             kfn = k_accel<false, false, false, false, true>;  // production, recording wall time
         }
+        if (ss_fused) {
+            // the same choice among the supersampling instances (SS): no compaction, no records
+            if (c->accel.mt)
+                kfn = !k2.tile_cost  ? k_accel<false, false, false, true, false, false, true>
+                      : k2.cost_time ? k_accel<false, false, false, true, true, false, true>
+                                     : k_accel<false, true, false, true, true, false, true>;
+            else if (latency)
+                kfn = !k2.tile_cost  ? k_accel<false, false, true, false, false, false, true>
+                      : k2.cost_time ? k_accel<false, false, true, false, true, false, true>
+                                     : k_accel<false, true, true, false, true, false, true>;
+            else
+                kfn = !k2.tile_cost  ? k_accel<false, false, false, false, false, false, true>
+                      : k2.cost_time ? k_accel<false, false, false, false, true, false, true>
+                                     : k_accel<false, true, false, false, true, false, true>;
+        }
         const bool tail_on = k2.tail_queue != nullptr;
         // one wave per dispatch slot: the split heavy tiles' extra waves too
         const int blocks = k2.tiles + k2.heavy_k * (k2.heavy_parts - 1);
@@ -4693,6 +4832,7 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
             hipLaunchKernelGGL(k_accel_tail, dim3(tgrid), dim3(64), tlds, c->stream, A, c->mat, k2);
             c->tail_parity = 1 - c->tail_parity;
         }
+        if (ss && !ss_fused) launch_box_filter(c, kin);
         if (k2.tile_cost) {
             // the next frame's order; stream-ordered after this dispatch (and after its
             // end event, so rt_kernel_times is the render kernel alone), before the next
@@ -4734,6 +4874,7 @@ int launch(rt_ctx* c, const KParams& kp, bool stats) {
     } else {
         hipLaunchKernelGGL(k_packet, grid, dim3(kBlock), 0, c->stream, c->geo_leaf, c->geo_lin, c->mat, c->nodes,
                            kp);
+        if (ss) launch_box_filter(c, kin);
     }
     c->last_kind = stats ? RT_KERNEL_LANE : kind;
     HIP_TRY(hipGetLastError());
@@ -4898,6 +5039,7 @@ int rt_destroy(rt_ctx* c) {
     hipFree(c->staging_nodes);
     hipFree(c->staging_idx);
     hipFree(c->img);
+    hipFree(c->ss_buf);
     hipFree(c->stats_dev);
     hipFree(c->tail_queue);
     hipFree(c->tail_counts);
@@ -5273,10 +5415,32 @@ int rt_dispatch_rows_ex(rt_ctx* c, int width, int height, int y0, int stripe, in
                         size_t pitch, int format) {
     if (!c) return RT_ERR_INVALID;
     KParams kp;
-    int rc = fill_kparams(c, width, height, y0, stripe, period, out_rows, dst, pitch, kp, format);
+    const int n = c->samples;
+    if (n > 1) {
+        // rt_set_samples: the sample frame is the same mapping with every extent times n.
+        // Refused before anything is launched when it breaks a limit of the one-sample
+        // dispatch: an int overflows, more than 65535 tile rows, width * rows >= 2^32.
+        const long long lim = INT_MAX / n;
+        if (width > lim || height > lim || y0 > lim || stripe > lim || period > lim || out_rows > lim ||
+            width < 0 || height < 0 || y0 < 0 || stripe < 0 || period < 0 || out_rows < 0)
+            return RT_ERR_INVALID;
+        if (width > 0 && out_rows > 0 &&
+            ((static_cast<long long>(out_rows) * n + kTileH - 1) / kTileH > 65535 ||
+             static_cast<unsigned long long>(width) * n * (static_cast<unsigned long long>(out_rows) * n) >=
+                 (1ull << 32)))
+            return RT_ERR_INVALID;
+    }
+    int rc = fill_kparams(c, width * n, height * n, y0 * n, stripe * n, period * n, out_rows * n, dst, pitch, kp,
+                          format, n);
     if (rc != RT_OK) return rc;
     if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
     return render(c, kp);
+}
+
+int rt_set_samples(rt_ctx* c, int n) {
+    if (!c || (n != 1 && n != 2 && n != 4 && n != 8)) return RT_ERR_INVALID;
+    c->samples = n;
+    return RT_OK;
 }
 
 int rt_dispatch(rt_ctx* c, int width, int height, int y0, int y1) {
@@ -5682,6 +5846,15 @@ extern "C" int rt_debug_split(rt_ctx* c, int max_rays, int group) {
     if (!c || max_rays < 0 || max_rays > 32 || group < 2 || group > 64 || (group & (group - 1))) return RT_ERR_INVALID;
     c->split_max = max_rays;
     c->split_g = group;
+    return RT_OK;
+}
+
+// Diagnostics: supersampled frames (rt_set_samples) take the general path -- the sample
+// frame into the scratch surface, then k_box_filter -- even where k_accel would reduce the
+// samples in its store. Same image either way (tests, tools/bench_ss.py's baseline).
+extern "C" int rt_debug_ss_general(rt_ctx* c, int on) {
+    if (!c) return RT_ERR_INVALID;
+    c->ss_general = on != 0;
     return RT_OK;
 }
 

@@ -219,6 +219,7 @@ RT_SYMBOLS = {
     "rt_set_latency_mode": (_I, [_P, _I]),
     "rt_set_kernel_timing": (_I, [_P, _I]),
     "rt_set_tail": (_I, [_P, _I]),
+    "rt_set_samples": (_I, [_P, _I]),
     "rt_status_string": (C.c_char_p, [_I]),
 }
 
@@ -706,6 +707,18 @@ class ComputeShader:
     def set_tail(self, from_bounce):
         """Bounces >= from_bounce of the rays still alive run compacted in a second kernel; 0 = off."""
         self._chk(self._lib.rt_set_tail(self._h, int(from_bounce)), "rt_set_tail")
+
+    def set_samples(self, n):
+        """rt_set_samples: every pixel is the mean of n x n samples (n in 1, 2, 4, 8) on the regular
+        sub-pixel grid, i.e. the box filter of the n*W x n*H frame; applies to every dispatch form."""
+        self._chk(self._lib.rt_set_samples(self._h, int(n)), "rt_set_samples")
+
+    def debug_ss_general(self, on):
+        """Diagnostics: supersampled frames render the sample frame and filter it with a second
+        kernel even where the accelerated kernel would average the samples in its store."""
+        fn = self._lib.rt_debug_ss_general
+        fn.argtypes = [_P, _I]
+        self._chk(fn(self._h, int(bool(on))), "rt_debug_ss_general")
 
     def debug_shadow_walk(self, from_bounce):
         fn = self._lib.rt_debug_shadow_walk
