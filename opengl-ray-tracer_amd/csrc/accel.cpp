@@ -1291,6 +1291,69 @@ void parallel_for(int n, int min_per_thread, const std::function<void(int, int)>
     parallel_chunks(n, min_per_thread, [&](int i0, int i1, int) { fn(i0, i1); });
 }
 
+bool local_prim_ranges(const AccelHost& A, std::vector<int>& first, std::vector<int>& end) {
+    const size_t M = A.lbox.size();
+    first.assign(M, 0);
+    end.assign(M, 0);
+    for (size_t j = M; j-- > 0;) {  // children have larger indices than their parent
+        if (A.la[j] < 0) {
+            first[j] = -A.la[j] - 1;
+            end[j] = first[j] + A.lb[j];
+        } else {
+            const int l = A.la[j], r = A.lb[j] & 0x3fffffff;
+            if (end[l] != first[r]) return false;  // not contiguous: cannot happen
+            first[j] = first[l];
+            end[j] = end[r];
+        }
+    }
+    return true;
+}
+
+void scene_prim_ranges(const SceneTree& T, std::vector<int>& first, std::vector<int>& end) {
+    const size_t Ms = T.box.size();
+    first.assign(Ms, -1);
+    end.assign(Ms, -1);
+    std::function<void(int)> range = [&](int j) {
+        if (first[j] >= 0) return;
+        if (T.a[j] < 0) {
+            first[j] = -T.a[j] - 1;
+            end[j] = first[j] + T.b[j];
+            return;
+        }
+        const int l = T.a[j], r = T.b[j] & 0x3fffffff;
+        range(l);
+        range(r);
+        first[j] = first[l];
+        end[j] = end[r];
+    };
+    for (size_t j = 0; j < Ms; ++j) range(static_cast<int>(j));
+}
+
+std::vector<int> wide_slot_table(const AccelHost& A) {
+    const size_t nlw = A.wchild.size();
+    const SceneTree& T = A.st;
+    const size_t nsw = T.wroot >= 0 ? T.wchild.size() : 0;
+    std::vector<int> tab(4 * (nlw + nsw), 0), first, end;
+    if (!local_prim_ranges(A, first, end)) return std::vector<int>();
+    for (size_t q = 0; q < nlw; ++q)
+        if (const int j = A.wchild[q]; j >= 0) {
+            tab[4 * q] = 1;
+            tab[4 * q + 1] = first[j];
+            tab[4 * q + 2] = end[j];
+        }
+    if (nsw == 0) return tab;
+    scene_prim_ranges(T, first, end);
+    for (size_t q = 0; q < nsw; ++q)
+        if (const int j = T.wchild[q]; j >= 0) {
+            int* t = &tab[4 * (nlw + q)];
+            t[0] = 1;
+            t[1] = first[j];
+            t[2] = end[j];
+            t[3] = 1 | (A.st_cone[4 * static_cast<size_t>(j) + 3] <= kNoPrune ? 2 : 0);
+        }
+    return tab;
+}
+
 bool build_accel(const FlatShape* shapes, int S, const FlatNode* nodes, int N, const int* idx, int I,
                  int leaf_threshold, int stack_cap, AccelHost& out, bool mt) {
     (void)I;

@@ -132,6 +132,16 @@ void build_cones(const FlatShape* shapes, AccelHost& A);
 // first chunk. Exceptions reach the caller after every chunk ended.
 void parallel_for(int n, int min_per_thread, const std::function<void(int, int)>& fn);
 
+// The prim range [first, end) below every local node (a subtree's prims are contiguous:
+// LocalBuilder emits them together; false if they are not) and below every scene-tree
+// node, for the refit's slot lists (rt_kernels.hip prepare_animation) and its dump.
+bool local_prim_ranges(const AccelHost& A, std::vector<int>& first, std::vector<int>& end);
+void scene_prim_ranges(const SceneTree& T, std::vector<int>& first, std::vector<int>& end);
+// Per wide slot 4*w + s of the device's wide records (the local ones, then the scene
+// tree's), 4 ints: has a child, first prim, end prim, bit 0 scene tree | bit 1 kNoPrune
+// (diagnostics: rt_debug_accel_dump). Empty if the local prims are not contiguous.
+std::vector<int> wide_slot_table(const AccelHost& A);
+
 constexpr int kWide = 4;  // children per wide record (one 128-byte record of the barycentric accelerator)
 // Children per wide node of the barycentric accelerators: 8 = two consecutive records
 // tested at one step (half as many... log8 instead of log4 dependent node steps per

@@ -3568,18 +3568,8 @@ int prepare_animation(rt_ctx* c) {
         }
     lap("local maps");
         // prim range of every local subtree (contiguous: LocalBuilder emits a subtree's prims together)
-        std::vector<int> first(M, 0), end(M, 0);
-        for (size_t j = M; j-- > 0;) {  // children have larger indices than their parent
-            if (A.la[j] < 0) {
-                first[j] = -A.la[j] - 1;
-                end[j] = first[j] + A.lb[j];
-            } else {
-                const int l = A.la[j], r = A.lb[j] & 0x3fffffff;
-                if (end[l] != first[r]) return RT_ERR_BVH;  // not contiguous: cannot happen
-                first[j] = first[l];
-                end[j] = end[r];
-            }
-        }
+        std::vector<int> first, end;
+        if (!rta::local_prim_ranges(A, first, end)) return RT_ERR_BVH;
         std::vector<int4> work;
         for (size_t j = 0; j < M; ++j)
             if (dirty[j]) work.push_back(make_int4(wpos[j], first[j], end[j], 0));
@@ -3592,27 +3582,17 @@ int prepare_animation(rt_ctx* c) {
         const rta::SceneTree& T = A.st;
         if (T.wroot >= 0) {
             const size_t nw = A.wchild.size() / rta::kWide, Ms = T.box.size();
-            std::vector<int> sparent(Ms, -1), swpos(Ms, -1), sfirst(Ms, -1), send(Ms, -1), sleaf(P, -1);
+            std::vector<int> sparent(Ms, -1), swpos(Ms, -1), sfirst, send, sleaf(P, -1);
             for (size_t j = 0; j < Ms; ++j) {
                 if (T.a[j] < 0) {
                     const int st = -T.a[j] - 1;
-                    sfirst[j] = st;
-                    send[j] = st + T.b[j];
                     for (int q = 0; q < T.b[j]; ++q) sleaf[st + q] = static_cast<int>(j);
                 } else {
                     sparent[T.a[j]] = static_cast<int>(j);
                     sparent[T.b[j] & 0x3fffffff] = static_cast<int>(j);
                 }
             }
-            std::function<void(int)> range = [&](int j) {
-                if (sfirst[j] >= 0) return;
-                const int l = T.a[j], r = T.b[j] & 0x3fffffff;
-                range(l);
-                range(r);
-                sfirst[j] = sfirst[l];
-                send[j] = send[r];
-            };
-            for (size_t j = 0; j < Ms; ++j) range(static_cast<int>(j));
+            rta::scene_prim_ranges(T, sfirst, send);
             for (size_t q = 0; q < T.wchild.size(); ++q)
                 if (T.wchild[q] >= 0) swpos[T.wchild[q]] = static_cast<int>(4 * nw + q);
             auto noprune = [&](int j) { return A.st_cone[4 * static_cast<size_t>(j) + 3] <= rta::kNoPrune; };
@@ -4331,6 +4311,7 @@ void inherit(rt_ctx* b, const rt_ctx* c) {
     b->moving_split = c->moving_split;
     b->frame_event = c->frame_event;
     b->refit_mode = c->refit_mode;
+    b->async_rebuild = c->async_rebuild;
     b->tail_from = c->tail_from;
     b->tail_max_lanes = c->tail_max_lanes;
     b->shadow_walk_override = c->shadow_walk_override;
@@ -5660,6 +5641,95 @@ extern "C" int rt_debug_refit_stats(rt_ctx* c, long long* out) {
     out[4] = static_cast<long long>(c->refit_ids.size());
     out[5] = c->last_flush_bytes;
     out[6] = c->refit_compactions;
+    return RT_OK;
+}
+
+// Diagnostics: the device state the refit maintains, read back for checking against a
+// plain recomputation (tests/refit_ref.py). which: 0 this context, 1 its brute-force
+// sub-context, 2 its Moller-Trumbore one (RT_ERR_INVALID while that does not exist or
+// does not hold the current scene). Section -1 applies the pending updates as a dispatch
+// applies them (flush_updates) and waits for the stream; the other sections copy the
+// state as that left it. Nothing a frame depends on changes. *need gets the section's
+// size in bytes; it is copied when cap holds it (dst null: the size only).
+// Sections 0-11, device arrays byte for byte: staging_shapes, staging_nodes, packed
+// nodes, geo_lin, geo_leaf, mat, prims, anodes, wnodes, titems, lnodes, pbox (empty
+// without an accelerator; pbox empty without a refit set). Host facts about topology:
+// 12 int info {record stride, mt, cone_cull, local wide records, all wide records, prims,
+// S, N, I, titems records, few-leaf count, refit entries, accelerator built}; 13 float
+// {origin_lim, mt_z xyz}; 14 wide_slot_table; 15 prim_shape; 16 per shape the class the
+// accelerator's boxes stand for (a refit entry's at the build, else as last classified);
+// 17 per titems record its reference leaf; 18 per shape its refit entry (-1: none).
+extern "C" int rt_debug_accel_dump(rt_ctx* c, int which, int section, void* dst, long long cap, long long* need) {
+    if (!c || !c->have_scene || !need || which < 0 || which > 2 || section < -1 || section > 18) return RT_ERR_INVALID;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    rt_ctx* x = which == 0 ? c : which == 1 ? c->brute : c->mtc;
+    if (!x || !x->have_scene || (which == 1 && c->brute_stale) || (which == 2 && c->mtc_stale)) return RT_ERR_INVALID;
+    if (section == -1) {
+        // one flush per dump, of the dumped context alone (a sub-context was given the writes when
+        // they were made): a second flush may land the rebuild that the first one's refit asked for
+        if (const int rc = flush_updates(x)) return rc;
+        *need = 0;
+    }
+    HIP_TRY(sync_stream(c));  // the sub-contexts run on this stream
+    if (section == -1) return RT_OK;
+    const rta::AccelHost& A = x->accel;
+    const bool acc = x->accel_ok;
+    const size_t S = x->S, N = x->N, I = x->I, P = acc ? A.prim_shape.size() : 0;
+    const size_t rec = A.mt ? kWideRecMt : kWideRec;
+    const size_t nlw = acc ? A.wchild.size() / rta::kWide : 0;
+    const size_t nsw = acc && A.st.wroot >= 0 ? A.st.wchild.size() / rta::kWide : 0;
+    const size_t f4 = sizeof(float4);
+    const void* dev = nullptr;
+    std::vector<int> hi;
+    std::vector<float> hf;
+    size_t bytes = 0;
+    switch (section) {
+        case 0: dev = x->staging_shapes, bytes = S * sizeof(FlatShape); break;
+        case 1: dev = x->staging_nodes, bytes = N * sizeof(FlatNode); break;
+        case 2: dev = x->nodes, bytes = 2 * N * f4; break;
+        case 3: dev = x->geo_lin, bytes = 5 * S * f4; break;
+        case 4: dev = x->geo_leaf, bytes = 5 * I * f4; break;
+        case 5: dev = x->mat, bytes = 2 * S * f4; break;
+        case 6: dev = x->prims, bytes = acc ? 4 * P * f4 : 0; break;
+        case 7: dev = x->anodes, bytes = acc ? 4 * N * f4 : 0; break;
+        case 8: dev = x->wnodes, bytes = acc ? 8 * N * f4 : 0; break;
+        case 9: dev = x->titems, bytes = acc ? 2 * static_cast<size_t>(x->n_titems) * f4 : 0; break;
+        case 10: dev = x->lnodes, bytes = acc ? rec * (nlw + nsw) * f4 : 0; break;
+        case 11: dev = x->pbox, bytes = acc && x->pbox ? 2 * P * f4 : 0; break;
+        case 12:
+            hi = {static_cast<int>(rec), A.mt ? 1 : 0, x->cone_cull, static_cast<int>(nlw), static_cast<int>(nlw + nsw),
+                  static_cast<int>(P), x->S, x->N, x->I, x->n_titems, x->nfew, static_cast<int>(x->refit_ids.size()),
+                  acc ? 1 : 0};
+            break;
+        case 13: hf = {A.origin_lim, A.mt_z[0], A.mt_z[1], A.mt_z[2]}; break;
+        case 14:
+            if (acc) hi = rta::wide_slot_table(A);
+            break;
+        case 15:
+            if (acc) hi = A.prim_shape;
+            break;
+        case 16:
+            if (acc && A.shape_cls.size() == S) {
+                hi = A.shape_cls;
+                for (size_t i = 0; i < x->refit_ids.size() && i < x->anim_cls.size(); ++i)
+                    hi[x->refit_ids[i]] = x->anim_cls[i];
+            }
+            break;
+        case 17:
+            if (acc) hi = x->host_titem_ref;
+            break;
+        default: hi = x->refit_of; break;
+    }
+    if (section >= 12) bytes = section == 13 ? hf.size() * sizeof(float) : hi.size() * sizeof(int);
+    *need = static_cast<long long>(bytes);
+    if (!dst || bytes == 0) return RT_OK;
+    if (cap < static_cast<long long>(bytes)) return RT_ERR_INVALID;
+    if (section >= 12) {
+        std::memcpy(dst, section == 13 ? static_cast<const void*>(hf.data()) : static_cast<const void*>(hi.data()), bytes);
+        return RT_OK;
+    }
+    if (!dev) return RT_ERR_INVALID;
+    HIP_TRY(hipMemcpy(dst, dev, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

@@ -832,6 +832,37 @@ class ComputeShader:
         return dict(zip(["dirty_slots", "max_range", "sum_range", "nodes", "entries", "flush_bytes", "compactions"],
                         out.tolist()))
 
+    _DUMP = [("staging_shapes", SHAPE_DTYPE), ("staging_nodes", NODE_DTYPE), ("nodes", "<f4"), ("geo_lin", "<f4"),
+             ("geo_leaf", "<f4"), ("mat", "<f4"), ("prims", "<f4"), ("anodes", "<f4"), ("wnodes", "<f4"),
+             ("titems", "<f4"), ("lnodes", "<f4"), ("pbox", "<f4"), ("info", "<i4"), ("finfo", "<f4"),
+             ("slots", "<i4"), ("prim_shape", "<i4"), ("shape_cls", "<i4"), ("titem_ref", "<i4"), ("refit_of", "<i4")]
+
+    def debug_accel_dump(self, which="own"):
+        """rt_debug_accel_dump: the device state the refit maintains (pending updates applied
+        first, as a dispatch does) and the host's topology facts, as numpy arrays. which:
+        "own", "brute" or "mtc" (RTError -1 while that sub-context does not exist). float4
+        arrays come as (n, 4) float32, `slots` as (wide slots, 4) int32 (has a child, first
+        prim, end prim, 1 scene tree | 2 kNoPrune); the info words are also unpacked by name."""
+        fn = self._lib.rt_debug_accel_dump
+        fn.restype = C.c_int
+        fn.argtypes = [_P, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
+        w = {"own": 0, "brute": 1, "mtc": 2}[which]
+        out = {}
+        need = np.zeros(1, np.int64)
+        self._chk(fn(self._h, w, -1, None, 0, need.ctypes.data), "rt_debug_accel_dump")  # flush, once
+        for sec, (name, dt) in enumerate(self._DUMP):
+            self._chk(fn(self._h, w, sec, None, 0, need.ctypes.data), "rt_debug_accel_dump")
+            a = np.zeros(int(need[0]) // np.dtype(dt).itemsize, dt)
+            if a.size:
+                self._chk(fn(self._h, w, sec, a.ctypes.data, a.nbytes, need.ctypes.data), "rt_debug_accel_dump")
+            out[name] = a.reshape(-1, 4) if (dt == "<f4" and name != "finfo") or name == "slots" else a
+        for k, v in zip(["rec", "mt", "cone_cull", "n_local_wide", "n_wide", "P", "S", "N", "I", "n_titems", "nfew",
+                         "n_refit", "built"], out["info"].tolist()):
+            out[k] = v
+        out["origin_lim"] = np.float32(out["finfo"][0])
+        out["mt_z"] = out["finfo"][1:4].copy()
+        return out
+
     def debug_moving(self, period, dilate, split):
         """Cost order of dispatches whose camera moved: re-derived every `period` frames
         (0: as still frames), over costs dilated by `dilate` tiles, split tiles kept on

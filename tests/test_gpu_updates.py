@@ -95,7 +95,7 @@ def test_reference_upload_loop_matches_oracle(ctx, cfg):
     same(ctx.render(W, H), last, "rt_animate against the reference's upload")
 
 
-def _soup(seed, n_tri=1500):
+def _soup(seed, n_tri=1500, depth=6):
     rng = np.random.default_rng(seed)
     sc = rtamd.Scene()
     for i in range(n_tri):
@@ -111,7 +111,7 @@ def _soup(seed, n_tri=1500):
     sc.set_camera((5, -25, 45), 60, 4 / 3)
     sc.LookAt((0, 0, 0))
     sc.set_light((10, -30, 20), (1, 1, 1), 40)
-    sc.buildBVH(6)
+    sc.buildBVH(depth)
     return sc.serializeScene()
 
 
