@@ -16,6 +16,10 @@ host's current records alone and returns the violations, each (array, where, pri
   towards the previous dump's axis, and neither the opening nor the slab is given up
   (k[3] = 2, k[9] infinite) without its reason.
 
+grown_nodes(fs, ids, frames) gives the node records a group's frame slot must hold after the
+frames given to the group (updateBVH once per frame), and shifted() builds frames that each leave
+a trace in them (tests/test_group_refit_cpu.py, tests/test_gpu_group_refit_state.py).
+
 Only four product functions are used as they are (tests/native/refit_ref.cpp): classify,
 classify_mt_tight's constants, cone_culls_q with ray_consts, and the cone word's fields.
 Everything else is numpy in float64 or exact float32 min / max.
@@ -110,6 +114,49 @@ def host_dump(fs, mt):
     out["origin_lim"] = np.float32(out["finfo"][0])
     out["mt_z"] = out["finfo"][1:4].copy()
     return out
+
+
+# ---------------------------------------------------------------------------
+# the frames of a group's deferred growth (tests/test_gpu_group_refit_state.py)
+
+SHIFT_DIRS = np.array([[1, 0, 0], [0, -1, 0], [0, 0, 1], [-1, 0, 0], [0, 1, 0], [0, 0, -1]], np.float32)
+
+
+def grown_nodes(fs, ids, frames):
+    """The node records after updateBVH (rtamd.update_bvh) once per frame, in order, from the
+    scene's own: what every node-box copy of every frame slot must hold once the slot has
+    flushed, whichever of the frames it rendered. frames: the records of `ids`, in that order."""
+    h = rtamd.FlatScene(fs.shapes.copy(), fs.nodes.copy(), fs.indices, fs.camera, fs.light)
+    ids = np.ascontiguousarray(ids, np.int32)
+    for f in frames:
+        h.shapes[ids] = f
+        rtamd.update_bvh(h, ids)
+    return h.nodes
+
+
+def shifted(shapes, ids, k, step=64.0):
+    """`shapes` with the shapes `ids` shifted by `step` along direction k of +x, -y, +z, -x, +y,
+    -z (from the seventh frame on by twice the step, and so on): a sphere's centre, a wall's
+    start, a triangle's vertices with planeD through the new first vertex. With a step above
+    the scene's extent every frame of six sets an extreme of the boxes no other frame sets."""
+    s = shapes.copy()
+    d = SHIFT_DIRS[k % 6] * np.float32(step * (1 + k // 6))
+    for i in ids:
+        t = s["type"][i]
+        if t == rtamd.SPHERE:
+            s["sphereCenter"][i] += d
+        elif t == rtamd.WALL:
+            s["wallStart"][i] += d
+        elif t == rtamd.TRIANGLE:
+            for f in ("triP1", "triP2", "triP3"):
+                s[f][i] += d
+            s["planeD"][i] = np.float32(-(s["planeNormal"][i].astype(np.float64) @ s["triP1"][i].astype(np.float64)))
+    return s
+
+
+def boxes_differ(a, b):
+    """the nodes whose box differs between two node arrays, bit for bit"""
+    return np.where((_u(a["boundsMin"]) != _u(b["boundsMin"])).any(1) | (_u(a["boundsMax"]) != _u(b["boundsMax"])).any(1))[0]
 
 
 # ---------------------------------------------------------------------------

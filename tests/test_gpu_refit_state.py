@@ -14,8 +14,8 @@ with buildBVH(6) (more than 8 reference leaves: one titems record per scene-tree
 with buildBVH(2) (at most 8: the few-leaf titems layout, one record per leaf); the tests assert
 which layout each got. The builder lists every shape in exactly one leaf (asserted), so no moved
 set needs a shape listed twice. rt_debug_async_rebuild(0) throughout: a rebuild runs in the
-flush that finds its report. The growth-box path of group frame slots (AF_BOX) needs a group
-and remains unchecked here.
+flush that finds its report. The growth-box path of group frame slots (AF_BOX) needs a group:
+tests/test_gpu_group_refit_state.py checks it with the same reference.
 """
 import ctypes as C
 
@@ -317,6 +317,17 @@ def test_compaction(run_factory, mode):
     _move(r, np.union1d(A[:40], B), rng, 2, f"mode {mode} union")
 
 
+def _sliver(shapes, t):
+    """triangle t collapsed in place: its third vertex on the middle of its first edge"""
+    shapes["triP3"][t] = shapes["triP1"][t] + (shapes["triP2"][t] - shapes["triP1"][t]) * 0.5
+
+
+def _slots_above(d, t):
+    """the pruning slots whose prim range holds shape t"""
+    return [q for q in np.where((d["slots"][:, 0] == 1) & ((d["slots"][:, 3] & 2) == 0))[0]
+            if t in d["prim_shape"][d["slots"][q, 1]:d["slots"][q, 2]]]
+
+
 @pytest.mark.parametrize("mode", MODES)
 def test_kind_change(run_factory, mode):
     """A moved triangle collapses to a sliver: after that flush every slot above it is infinite
@@ -334,14 +345,13 @@ def test_kind_change(run_factory, mode):
     r.verify("moved")
     t = int(ids[fs.shapes["type"][ids] == 3][0])
     good = h.shapes[t:t + 1].copy()
-    h.shapes["triP3"][t] = h.shapes["triP1"][t] + (h.shapes["triP2"][t] - h.shapes["triP1"][t]) * 0.5
+    _sliver(h.shapes, t)
     r0 = r.ctx.debug_anim_rebuilds()
     r.ctx.update_shapes(t, h.shapes[t:t + 1])
     out = r.verify("sliver")
     assert r.ctx.debug_anim_rebuilds() == r0
     d = out["own"]
-    above = [q for q in np.where((d["slots"][:, 0] == 1) & ((d["slots"][:, 3] & 2) == 0))[0]
-             if t in d["prim_shape"][d["slots"][q, 1]:d["slots"][q, 2]]]
+    above = _slots_above(d, t)
     assert above, "the sliver's triangle is under no slot"
     sb = rr.slot_boxes(d)[above]
     assert np.all(sb[:, :3] == -np.inf) and np.all(sb[:, 3:] == np.inf)
