@@ -343,6 +343,64 @@ int rt_read_indices(struct rt_ctx* ctx, int* indices, int num_indices);
 enum rt_tree { RT_TREE_REFERENCE = 0, RT_TREE_SCENE = 1 };
 int rt_set_tree(struct rt_ctx* ctx, int mode);
 
+/* Ray queries over the uploaded scene: picking, line of sight, distance along a ray.
+ *
+ * Every ray gets the answer of the reference's BVH branch (gpu_shader.comp:380-430) over
+ * the context's current tree and shapes: the closest INNER hit by distance, strict "<" in
+ * the reference's walk order, so ties go to the first shape the reference would find.
+ * rt_params::useBVH does not matter to a query; useMollerTrumbore selects the triangle
+ * test as for the next dispatch (barycentric if no params were ever set). Camera, light,
+ * bounces, Fresnel and rt_set_samples do not enter. rt_set_kernel and rt_set_tree apply
+ * as they do to frames: the accelerated walk (its Moller-Trumbore form for MT queries), or
+ * the literal reference walk for RT_KERNEL_LANE / RT_KERNEL_PACKET and scenes without an
+ * accelerator. Same answers either way. Rays are walked in the order given, 64 consecutive
+ * rays to a wave: coherent neighbours are faster.
+ *
+ * A query reads the device scene: like a dispatch it first applies pending
+ * rt_update_shapes / rt_update_nodes / rt_animate work as one refit, so it sees the scene
+ * the next frame would see. It does not touch the context surface, rt_accel_info::
+ * last_kernel, the record of rt_kernel_times / rt_last_kernel_ms, rt_sync_frame's frame
+ * marker or the tile cost order.
+ *
+ * RT_TRACE_CLOSEST fills shape and distance, and occluded = (shape >= 0 && distance <
+ * limit). RT_TRACE_ANY is the shadow walk: it stops at the first INNER hit nearer than
+ * limit, fills occluded only and writes shape = -1, distance = 1e20f. */
+typedef struct rt_ray {      /* 32 bytes, 16-byte aligned */
+    float origin[3];
+    float limit;             /* occlusion limit: a distance from the origin, as the shader's light distance */
+    float dir[3];            /* any length; need not be normalised */
+    int   reserved;          /* 0 */
+} rt_ray;
+
+typedef struct rt_hit {      /* 16 bytes */
+    int   shape;             /* index into the uploaded FlatShape array, -1 = miss */
+    float distance;          /* the reference's distance(origin, hit point); 1e20f on a miss */
+    int   occluded;          /* 1 if an INNER hit lies nearer than rt_ray::limit, else 0 */
+    int   reserved;          /* 0 */
+} rt_hit;
+
+enum rt_trace_mode { RT_TRACE_CLOSEST = 0, RT_TRACE_ANY = 1 };
+
+RT_STATIC_ASSERT(sizeof(rt_ray) == 32 && offsetof(rt_ray, limit) == 12 && offsetof(rt_ray, dir) == 16, "rt_ray");
+RT_STATIC_ASSERT(sizeof(rt_hit) == 16 && offsetof(rt_hit, distance) == 4 && offsetof(rt_hit, occluded) == 8, "rt_hit");
+
+/* dev_rays / dev_hits are device pointers, 16-byte aligned; stream-ordered on the context's
+ * stream, asynchronous. RT_ERR_INVALID: a null pointer with n > 0, n < 0, an unknown mode,
+ * a misaligned pointer. RT_ERR_NO_SCENE before rt_upload_scene. n == 0 launches nothing.
+ * A scene without nodes answers every ray with a miss. */
+int rt_trace_rays(struct rt_ctx* ctx, const rt_ray* dev_rays, int n, rt_hit* dev_hits, int mode);
+
+/* The same with host pointers, staged through buffers the context keeps between calls;
+ * returns when the hits are in `hits`. */
+int rt_trace_rays_host(struct rt_ctx* ctx, const rt_ray* rays, int n, rt_hit* hits, int mode);
+
+/* Picking: RT_TRACE_CLOSEST with an infinite limit for the camera ray of each pixel
+ * (xy[2i], xy[2i+1]) of a width x height frame, generated on the device exactly as a
+ * dispatch generates it (current camera, rt_params::resX / resY). Host pointers;
+ * synchronous. RT_ERR_NO_SCENE without a camera or params, RT_ERR_INVALID for a pixel
+ * outside the frame. */
+int rt_trace_pixels(struct rt_ctx* ctx, int width, int height, const int* xy, int n, rt_hit* hits);
+
 /* Accelerator statistics for the uploaded scene. */
 int rt_accel_info_get(struct rt_ctx* ctx, rt_accel_info* out);
 

@@ -31,6 +31,10 @@
 //       N x N box filter of a sample frame the kernels above rendered.
 //   k_accel_tail    : the remaining bounces of the rays k_accel queued
 //       (rt_set_tail), 64 rays from one screen region to a wave.
+//   k_trace<MODE, MT> / k_trace_ref<MODE> : ray queries (rt_trace_rays, rt_trace_pixels):
+//       the caller's rays, or the camera rays of the caller's pixels, one per lane
+//       through lane_walk over the accelerator (k_trace) or through k_lane's literal
+//       walk (k_trace_ref); closest hit or occlusion within a limit per ray.
 //   k_tile_order / k_cost_dilate : the next frame's dispatch order from the tile
 //       costs a k_accel dispatch recorded (rt_set_schedule).
 //   k_refit / k_inf_slots : boxes and cones of moved shapes (rt_animate,
@@ -1986,6 +1990,113 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel_tail(AccelPtrs A
         for (int b = threadIdx.x; b < kp.tail_counters; b += blockDim.x) kp.tail_count_next[b] = 0;
 }
 
+// ---------------------------------------------------------------------------
+// Ray queries (rt_trace_rays / rt_trace_rays_host / rt_trace_pixels): the walks above for
+// rays the caller gives, one ray per lane in the order given, answered as rt_hit records.
+
+struct TraceArgs {
+    const float4* __restrict__ rays;  // rt_ray: origin | limit, dir | reserved (unused with xy)
+    const int2* __restrict__ xy;      // rt_trace_pixels: the pixels whose camera rays are traced, else null
+    float4* __restrict__ hits;        // rt_hit, one 16-byte store per ray
+    int n;
+};
+
+// Ray i and its occlusion limit: two 16-byte loads, or the kernels' own camera ray of
+// pixel xy[i] with an infinite limit.
+__device__ __forceinline__ Ray trace_ray(const TraceArgs& q, const KParams& kp, int i, float& lim) {
+    if (q.xy) {
+        const int2 p = q.xy[i];
+        lim = INFINITY;
+        return primary_ray(kp, p.x, p.y);
+    }
+    const float4 a = q.rays[2 * static_cast<size_t>(i)], b = q.rays[2 * static_cast<size_t>(i) + 1];
+    lim = a.w;
+    return Ray{mk(a.x, a.y, a.z), mk(b.x, b.y, b.z)};
+}
+
+__device__ __forceinline__ void store_hit(const TraceArgs& q, int i, int shape, float d, bool occluded) {
+    q.hits[i] = make_float4(__int_as_float(shape), d, __int_as_float(occluded ? 1 : 0), 0.0f);
+}
+
+// MODE: rt_trace_mode. One wave per block over the accelerator, with k_accel_tail's LDS
+// stacks and the plain (non-split) lane_walk: closest form, or shadow form with the ray's
+// own limit. The winner's distance is the walk's Best::d, its shape AccelPtrs::prim_shape.
+template <int MODE, bool MT>
+__global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_trace(AccelPtrs A, TraceArgs q, KParams kp) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    unsigned short* stt =
+        reinterpret_cast<unsigned short*>(lds_stack + static_cast<size_t>(kp.lane_stack) * blockDim.x) + threadIdx.x;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = i < q.n;
+    Ray r{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 1.f)};
+    float lim = 0.f;
+    if (active) r = trace_ray(q, kp, i, lim);
+    WalkCount wc{0u, 0u, 0u, 0u};
+    Best b{1e20f, 0x7fffffff, 0.f, -1};
+    bool shadow = false;
+    if (MODE == RT_TRACE_ANY) {
+        lane_walk<true, false, false, MT, true>(A, r, active, gmin(lim, 1e20f), b, shadow, stk, stt, blockDim.x,
+                                                kp.lane_stack, wc);
+        if (active) store_hit(q, i, -1, 1e20f, shadow);
+    } else {
+        lane_walk<false, false, false, MT, true>(A, r, active, 0.f, b, shadow, stk, stt, blockDim.x, kp.lane_stack,
+                                                 wc);
+        if (active) store_hit(q, i, b.slot >= 0 ? A.prim_shape[b.slot] : -1, b.d, b.slot >= 0 && b.d < lim);
+    }
+}
+
+// The shadow counterpart of lane_closest_bvh: the same walk and intersection, ended by the
+// first INNER hit nearer than ld (the reference's closest hit is nearer than ld exactly
+// when some hit is).
+__device__ bool lane_any_bvh(const KParams& kp, const float4* __restrict__ nodes, const float4* __restrict__ geo,
+                             Ray r, float ld, int* stk) {
+    if (kp.N <= 0) return false;
+    const V inv = inv_dir(r.d);
+    int sp = 1;
+    stk[0] = kp.N - 1;
+    while (sp > 0) {
+        --sp;
+        const int k = stk[sp * kBlock];
+        const float4 a = nodes[2 * k], b = nodes[2 * k + 1];
+        if (!ray_aabb(r.o, inv, mk(a.x, a.y, a.z), mk(b.x, b.y, b.z))) continue;
+        const int ia = __float_as_int(a.w), ib = __float_as_int(b.w);
+        if (ia < 0) {
+            const int start = -ia - 1;
+            for (int i = 0; i < ib; ++i) {
+                const Hit h = intersect(load_rec(geo, start + i), r, kp.useMT);
+                if (h.type == INNER && dist(r.o, h.p) < ld) return true;
+            }
+        } else {
+            if (sp + 2 > kp.max_stack) return false;
+            stk[sp * kBlock] = ia;
+            stk[(sp + 1) * kBlock] = ib;
+            sp += 2;
+        }
+    }
+    return false;
+}
+
+// The same queries over the reference tree alone, k_lane's literal walk (contexts without a
+// usable accelerator, RT_KERNEL_LANE / RT_KERNEL_PACKET): 256-thread blocks, k_lane's stacks.
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_trace_ref(TraceArgs q, KParams kp) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= q.n) return;
+    float lim;
+    const Ray r = trace_ray(q, kp, i, lim);
+    if (MODE == RT_TRACE_ANY) {
+        store_hit(q, i, -1, 1e20f, lane_any_bvh(kp, kp.nodes, kp.geo_leaf, r, gmin(lim, 1e20f), stk));
+    } else {
+        Counters c;
+        const LaneHit h = lane_closest_bvh<false>(kp, kp.nodes, kp.geo_leaf, r, stk, c);
+        const int shape = h.found ? __float_as_int(kp.geo_leaf[5 * static_cast<size_t>(h.slot)].y) : -1;
+        store_hit(q, i, shape, h.d, h.found && h.d < lim);
+    }
+}
+
 // The general path of rt_set_samples: the sample frame was rendered by any kernel into a
 // scratch surface (compact rows, RGBA32F); one thread per output pixel applies the box
 // filter in the order rt_api.h fixes -- log2 N pairwise rounds along x, then along y,
@@ -2862,6 +2973,13 @@ struct rt_ctx {
     FlatCamera cam{};
     FlatLight light{};
     rt_params params{0.f, 0.f, 0, 0, 0, 0};  // the reference's first frame sees zeros
+    bool have_params = false;                // rt_set_params was called (rt_trace_pixels needs resX / resY)
+    // rt_trace_rays_host / rt_trace_pixels: staging for the rays (or pixels) and the hits,
+    // grown on demand and kept between calls
+    float4* trace_in = nullptr;
+    size_t trace_in_cap = 0;
+    float4* trace_hits = nullptr;
+    size_t trace_hits_cap = 0;
     int kernel = RT_KERNEL_AUTO;
     int last_kind = 0;
     // own surface
@@ -4214,6 +4332,18 @@ size_t sched_set_words(int tiles) {
     return static_cast<size_t>((tiles + kOrderThreads - 1) / kOrderThreads) * kOrderBuckets;
 }
 
+// The camera terms of getRay (primary_ray).
+void fill_camera(const FlatCamera& cam, KParams& kp) {
+    kp.cam_pos = V{cam.Position.x, cam.Position.y, cam.Position.z};
+    kp.cam_front = V{cam.Front.x, cam.Front.y, cam.Front.z};
+    kp.cam_right = V{cam.Right.x, cam.Right.y, cam.Right.z};
+    kp.cam_up = V{cam.Up.x, cam.Up.y, cam.Up.z};
+    // gpu_shader.comp:156-157 (radians = deg * 0.0174532925..., glm/GLSL).
+    const float h = 2.0f * std::tan((cam.fov / 2.0f) * 0.01745329251994329576923690768489f);
+    kp.plane_h = h;
+    kp.plane_w = h * cam.aspectRatio;
+}
+
 // ss > 1 (rt_set_samples): width .. out_rows are the SAMPLE frame's, ss times the output
 // frame's that dst, pitch and format describe (KParams::ss); resX, resY are scaled to match.
 int fill_kparams(rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows, float* dst,
@@ -4234,15 +4364,7 @@ int fill_kparams(rt_ctx* c, int width, int height, int y0, int stripe, int perio
     kp.N = c->N;
     kp.I = c->I;
     kp.max_stack = c->max_stack < 1 ? 1 : c->max_stack;
-    const FlatCamera& cam = c->cam;
-    kp.cam_pos = V{cam.Position.x, cam.Position.y, cam.Position.z};
-    kp.cam_front = V{cam.Front.x, cam.Front.y, cam.Front.z};
-    kp.cam_right = V{cam.Right.x, cam.Right.y, cam.Right.z};
-    kp.cam_up = V{cam.Up.x, cam.Up.y, cam.Up.z};
-    // gpu_shader.comp:156-157 (radians = deg * 0.0174532925..., glm/GLSL).
-    const float h = 2.0f * std::tan((cam.fov / 2.0f) * 0.01745329251994329576923690768489f);
-    kp.plane_h = h;
-    kp.plane_w = h * cam.aspectRatio;
+    fill_camera(c->cam, kp);
     kp.light_pos = V{c->light.position.x, c->light.position.y, c->light.position.z};
     kp.light_color = V{c->light.color.x, c->light.color.y, c->light.color.z};
     kp.resX = c->params.resX * static_cast<float>(ss);  // a power of two: exact
@@ -4273,6 +4395,17 @@ int fill_kparams(rt_ctx* c, int width, int height, int y0, int stripe, int perio
 bool accel_usable(const rt_ctx* c, const KParams& kp) {
     const float cmag = std::max({std::fabs(kp.cam_pos.x), std::fabs(kp.cam_pos.y), std::fabs(kp.cam_pos.z)});
     return c->accel_ok && kp.useBVH && (kp.useMT != 0) == c->accel.mt && cmag <= c->accel.origin_lim;
+}
+
+// The accelerator's device records as the walks take them.
+AccelPtrs accel_ptrs(const rt_ctx* c) {
+    // Animated scenes keep the scene tree: rt_animate refits its boxes and items (prepare_animation).
+    // (off while a rebuild for node boxes that stopped nesting runs: st_suspended)
+    const int troot = c->tree_mode == RT_TREE_SCENE && !c->st_suspended ? c->st_root : kNoChild;
+    return AccelPtrs{c->anodes, c->prims, c->lnodes, c->wnodes, c->tleaf, c->titems, troot,
+                     c->scene_stack > 0 ? c->scene_stack : kMaxStack, c->nfew, c->N, c->accel.origin_lim,
+                     c->boxes_finite, c->split_max, c->split_g, c->prim_idx_dev,
+                     {c->accel.mt_z[0], c->accel.mt_z[1], c->accel.mt_z[2]}};
 }
 
 int launch(rt_ctx* c, const KParams& kp, bool stats);
@@ -4706,13 +4839,7 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
             HIP_TRY(hipMemsetAsync(c->heavy_acc, 0, need * sizeof(unsigned long long), c->stream));
             k2.heavy_acc = c->heavy_acc;
         }
-        // Animated scenes keep the scene tree: rt_animate refits its boxes and items (prepare_animation).
-        // (off while a rebuild for node boxes that stopped nesting runs: st_suspended)
-        const int troot = c->tree_mode == RT_TREE_SCENE && !c->st_suspended ? c->st_root : kNoChild;
-        const AccelPtrs A{c->anodes, c->prims, c->lnodes, c->wnodes, c->tleaf, c->titems, troot,
-                          c->scene_stack > 0 ? c->scene_stack : kMaxStack, c->nfew, kp.N, c->accel.origin_lim,
-                          c->boxes_finite, c->split_max, c->split_g, c->prim_idx_dev,
-                          {c->accel.mt_z[0], c->accel.mt_z[1], c->accel.mt_z[2]}};
+        const AccelPtrs A = accel_ptrs(c);
         // compaction: bounces >= tail_from of the rays still alive run in k_accel_tail
         k2.tail_queue = nullptr;
         // RT_TAIL_AUTO: from bounce 2 on scenes of many scene-tree items (measured: config 5's
@@ -4871,6 +4998,87 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
     return RT_OK;
 }
 
+// One query launch on the context's stream (rt_trace_rays and its host forms): pending
+// scene writes first, as one refit; then k_trace over the accelerator the next dispatch
+// would walk (the context's own, or mtc's for Moller-Trumbore), or k_trace_ref's literal
+// walk when there is none or rt_set_kernel chose the lane / packet kernel. None of the
+// render state (last_kind, the timing ring, the frame marker, the cost order) is touched.
+int trace_launch(rt_ctx* c, const float4* rays, const int2* xy, int n, float4* hits, int mode) {
+    if (const int rc = flush_updates(c)) return rc;
+    const bool mt = c->params.useMollerTrumbore != 0;
+    rt_ctx* t = c;
+    if (mt) {
+        KParams sel;
+        std::memset(&sel, 0, sizeof sel);
+        sel.useBVH = sel.useMT = 1;
+        if (rt_ctx* b = mt_ctx(c, sel)) {
+            if (const int rc = flush_updates(b)) return rc;
+            if (b->accel_ok) t = b;
+        }
+    }
+    const bool accel = (c->kernel == RT_KERNEL_AUTO || c->kernel == RT_KERNEL_ACCEL) && t->accel_ok &&
+                       t->accel.mt == mt;
+    KParams kp;
+    std::memset(&kp, 0, sizeof kp);
+    kp.geo_leaf = t->geo_leaf;
+    kp.geo_lin = t->geo_lin;
+    kp.nodes = t->nodes;
+    kp.S = t->S;
+    kp.N = t->N;
+    kp.I = t->I;
+    kp.max_stack = t->max_stack < 1 ? 1 : t->max_stack;
+    kp.useBVH = 1;
+    kp.useMT = mt ? 1 : 0;
+    kp.lane_stack = t->lane_stack_override > 0 ? t->lane_stack_override : t->accel.max_stack;
+    if (xy) {
+        fill_camera(c->cam, kp);
+        kp.resX = c->params.resX;
+        kp.resY = c->params.resY;
+    }
+    const TraceArgs q{rays, xy, hits, n};
+    const bool any = mode == RT_TRACE_ANY;
+    if (accel) {
+        auto kfn = mt ? (any ? k_trace<RT_TRACE_ANY, true> : k_trace<RT_TRACE_CLOSEST, true>)
+                      : (any ? k_trace<RT_TRACE_ANY, false> : k_trace<RT_TRACE_CLOSEST, false>);
+        const size_t lds = static_cast<size_t>(kp.lane_stack) * 64 * 6;
+        hipLaunchKernelGGL(kfn, dim3((n + 63) / 64), dim3(64), lds, c->stream, accel_ptrs(t), q, kp);
+    } else {
+        auto kfn = any ? k_trace_ref<RT_TRACE_ANY> : k_trace_ref<RT_TRACE_CLOSEST>;
+        const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
+        hipLaunchKernelGGL(kfn, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, c->stream, q, kp);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// The checks every query form shares; RT_OK with *run = false when there is nothing to launch.
+int trace_check(const rt_ctx* c, const void* in, int n, const void* hits, int mode, bool* run) {
+    *run = false;
+    if (!c || n < 0 || (mode != RT_TRACE_CLOSEST && mode != RT_TRACE_ANY) || (n > 0 && (!in || !hits)))
+        return RT_ERR_INVALID;
+    if (!c->have_scene) return RT_ERR_NO_SCENE;
+    *run = n > 0;
+    return RT_OK;
+}
+
+// Host queries: `in` (n records of in_bytes each: rt_ray, or a pixel's two ints) through
+// the context's staging buffers, the launch, and the hits back.
+int trace_staged(rt_ctx* c, const void* in, size_t in_bytes, bool pixels, int n, rt_hit* hits, int mode) {
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    const size_t in16 = (static_cast<size_t>(n) * in_bytes + 15) / 16;
+    int rc = ensure_staging(c->trace_in, c->trace_in_cap, in16);
+    if (rc == RT_OK) rc = ensure_staging(c->trace_hits, c->trace_hits_cap, static_cast<size_t>(n));
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->trace_in, in, static_cast<size_t>(n) * in_bytes, hipMemcpyHostToDevice, c->stream));
+    rc = trace_launch(c, pixels ? nullptr : c->trace_in, pixels ? reinterpret_cast<const int2*>(c->trace_in) : nullptr,
+                      n, c->trace_hits, mode);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(hits, c->trace_hits, static_cast<size_t>(n) * sizeof(rt_hit), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(sync_stream(c));
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5022,6 +5230,8 @@ int rt_destroy(rt_ctx* c) {
     hipFree(c->img);
     hipFree(c->ss_buf);
     hipFree(c->stats_dev);
+    hipFree(c->trace_in);
+    hipFree(c->trace_hits);
     hipFree(c->tail_queue);
     hipFree(c->tail_counts);
     hipFree(c->tile_times);
@@ -5366,6 +5576,7 @@ int rt_set_light(rt_ctx* c, const FlatLight* l) {
 int rt_set_params(rt_ctx* c, const rt_params* p) {
     if (!c || !p || p->maxBounces < 0) return RT_ERR_INVALID;
     c->params = *p;
+    c->have_params = true;
     return RT_OK;
 }
 
@@ -5575,6 +5786,33 @@ int rt_last_kernel_ms(rt_ctx* c, float* ms) {
     HIP_TRY(hipEventSynchronize(c->last1));
     HIP_TRY(hipEventElapsedTime(ms, c->last0, c->last1));
     return RT_OK;
+}
+
+int rt_trace_rays(rt_ctx* c, const rt_ray* dev_rays, int n, rt_hit* dev_hits, int mode) {
+    bool run;
+    if (const int rc = trace_check(c, dev_rays, n, dev_hits, mode, &run)) return rc;
+    if (!run) return RT_OK;
+    if (reinterpret_cast<uintptr_t>(dev_rays) % 16 != 0 || reinterpret_cast<uintptr_t>(dev_hits) % 16 != 0)
+        return RT_ERR_INVALID;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    return trace_launch(c, reinterpret_cast<const float4*>(dev_rays), nullptr, n, reinterpret_cast<float4*>(dev_hits),
+                        mode);
+}
+
+int rt_trace_rays_host(rt_ctx* c, const rt_ray* rays, int n, rt_hit* hits, int mode) {
+    bool run;
+    if (const int rc = trace_check(c, rays, n, hits, mode, &run)) return rc;
+    return run ? trace_staged(c, rays, sizeof(rt_ray), false, n, hits, mode) : RT_OK;
+}
+
+int rt_trace_pixels(rt_ctx* c, int width, int height, const int* xy, int n, rt_hit* hits) {
+    bool run;
+    if (const int rc = trace_check(c, xy, n, hits, RT_TRACE_CLOSEST, &run)) return rc;
+    if (!c->have_cam || !c->have_params) return RT_ERR_NO_SCENE;
+    if (width <= 0 || height <= 0) return RT_ERR_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (xy[2 * i] < 0 || xy[2 * i] >= width || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= height) return RT_ERR_INVALID;
+    return run ? trace_staged(c, xy, 2 * sizeof(int), true, n, hits, RT_TRACE_CLOSEST) : RT_OK;
 }
 
 }  // extern "C"

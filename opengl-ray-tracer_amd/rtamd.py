@@ -70,7 +70,23 @@ LIGHT_DTYPE = np.dtype({
     "itemsize": 32,
 })
 
+# rt_ray / rt_hit (include/rt_api.h): the records of the ray queries
+RAY_DTYPE = np.dtype({
+    "names": ["origin", "limit", "dir", "reserved"],
+    "formats": [("<f4", 3), "<f4", ("<f4", 3), "<i4"],
+    "offsets": [0, 12, 16, 28],
+    "itemsize": 32,
+})
+
+HIT_DTYPE = np.dtype({
+    "names": ["shape", "distance", "occluded", "reserved"],
+    "formats": ["<i4", "<f4", "<i4", "<i4"],
+    "offsets": [0, 4, 8, 12],
+    "itemsize": 16,
+})
+
 SPHERE, PLANE, WALL, TRIANGLE = 0, 1, 2, 3
+TRACE_CLOSEST, TRACE_ANY = 0, 1
 KERNEL_AUTO, KERNEL_LANE, KERNEL_PACKET, KERNEL_ACCEL = 0, 1, 2, 3
 SCHED_ROWS, SCHED_COST, SCHED_COST_XCD = 0, 1, 2
 TREE_REFERENCE, TREE_SCENE = 0, 1
@@ -220,6 +236,9 @@ RT_SYMBOLS = {
     "rt_set_kernel_timing": (_I, [_P, _I]),
     "rt_set_tail": (_I, [_P, _I]),
     "rt_set_samples": (_I, [_P, _I]),
+    "rt_trace_rays": (_I, [_P, _P, _I, _P, _I]),
+    "rt_trace_rays_host": (_I, [_P, _P, _I, _P, _I]),
+    "rt_trace_pixels": (_I, [_P, _I, _I, _P, _I, _P]),
     "rt_status_string": (C.c_char_p, [_I]),
 }
 
@@ -712,6 +731,42 @@ class ComputeShader:
         """rt_set_samples: every pixel is the mean of n x n samples (n in 1, 2, 4, 8) on the regular
         sub-pixel grid, i.e. the box filter of the n*W x n*H frame; applies to every dispatch form."""
         self._chk(self._lib.rt_set_samples(self._h, int(n)), "rt_set_samples")
+
+    @staticmethod
+    def make_rays(origins, dirs, limits=None):
+        """RAY_DTYPE records of n rays; limits default to infinity (any hit occludes)."""
+        origins = np.asarray(origins, np.float32).reshape(-1, 3)
+        rays = np.zeros(len(origins), RAY_DTYPE)
+        rays["origin"] = origins
+        rays["dir"] = np.asarray(dirs, np.float32).reshape(-1, 3)
+        rays["limit"] = np.inf if limits is None else np.asarray(limits, np.float32)
+        return rays
+
+    def trace_rays(self, origins, dirs, limits=None, any_hit=False):
+        """rt_trace_rays_host: the reference walk's closest INNER hit of each ray over the current
+        scene, as (shape, distance, occluded) arrays: shape index or -1, distance or 1e20, and
+        whether a hit lies nearer than the ray's limit. any_hit: the shadow walk (TRACE_ANY), which
+        fills occluded only (shape -1, distance 1e20)."""
+        rays = self.make_rays(origins, dirs, limits)
+        hits = np.zeros(len(rays), HIT_DTYPE)
+        self._chk(self._lib.rt_trace_rays_host(self._h, _ptr(rays), len(rays), _ptr(hits),
+                                               TRACE_ANY if any_hit else TRACE_CLOSEST), "rt_trace_rays_host")
+        return hits["shape"].copy(), hits["distance"].copy(), hits["occluded"].copy()
+
+    def trace_rays_device(self, rays_ptr, n, hits_ptr, mode=TRACE_CLOSEST):
+        """rt_trace_rays: n RAY_DTYPE records at device address rays_ptr (a torch tensor's
+        data_ptr()), HIT_DTYPE records to hits_ptr; stream-ordered, asynchronous."""
+        self._chk(self._lib.rt_trace_rays(self._h, C.c_void_p(rays_ptr) if rays_ptr else None, int(n),
+                                          C.c_void_p(hits_ptr) if hits_ptr else None, int(mode)), "rt_trace_rays")
+
+    def trace_pixels(self, width, height, xy):
+        """rt_trace_pixels: what the camera ray of each pixel (x, y) of a width x height frame
+        hits, as (shape, distance, occluded) arrays."""
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        hits = np.zeros(len(xy), HIT_DTYPE)
+        self._chk(self._lib.rt_trace_pixels(self._h, int(width), int(height), _ptr(xy), len(xy), _ptr(hits)),
+                  "rt_trace_pixels")
+        return hits["shape"].copy(), hits["distance"].copy(), hits["occluded"].copy()
 
     def debug_ss_general(self, on):
         """Diagnostics: supersampled frames render the sample frame and filter it with a second
