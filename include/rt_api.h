@@ -163,7 +163,8 @@ int rt_set_params(struct rt_ctx* ctx, const rt_params* params);
 int rt_set_kernel(struct rt_ctx* ctx, int kernel);
 
 /* glDispatchCompute(W,H,1) + glMemoryBarrier (src/main.cpp:352-354) into the
- * context's own W x H RGBA32F surface, rows [y0, y1). Stream-ordered, async. */
+ * context's own W x H surface (RGBA32F, or the format of rt_set_surface_format), rows
+ * [y0, y1). Stream-ordered, async. */
 int rt_dispatch(struct rt_ctx* ctx, int width, int height, int y0, int y1);
 
 /* Same into a caller-owned device surface (for tiling and RCCL gathers).
@@ -183,8 +184,34 @@ int rt_dispatch_rows(struct rt_ctx* ctx, int width, int height, int y0, int stri
  * RT_FORMAT_RGBA32F_IMAGE: RGBA32F written at each row's IMAGE row y, not at its
  * compact row r: dst is the whole width x height surface (pitch >= 16*width),
  * and rows the call does not render are left untouched. rt_group's rank 0
- * renders its stripes straight into the gathered frame this way. */
-enum rt_format { RT_FORMAT_RGBA32F = 0, RT_FORMAT_RGB32F = 1, RT_FORMAT_RGBA32F_IMAGE = 2 };
+ * renders its stripes straight into the gathered frame this way.
+ *
+ * Display formats: what a host that shows, encodes or saves the frame wants, converted in
+ * the render kernel's registers (and in the filter kernel of rt_set_samples), so nothing but
+ * the small pixel is written or read back. `dst` keeps its type but is a byte surface here.
+ * Per channel c, the float32 value the RGBA32F frame of the same dispatch would hold:
+ *   RT_FORMAT_RGBA8   4 B  q = (int)rintf(fminf(fmaxf(c, 0), 1) * 255.0f): the product in
+ *                          float32, rounded to nearest even; NaN gives 0.
+ *   RT_FORMAT_SRGBA8  4 B  R, G, B sRGB-encoded, alpha as RGBA8: q = the number of k in
+ *                          1..255 with clamp(c) >= T[k] (NaN gives 0), where T[k] is the
+ *                          float32 nearest to eotf((k - 0.5) / 255) evaluated in double,
+ *                          eotf(x) = x / 12.92 for x <= 0.04045, else ((x + 0.055) / 1.055)^2.4.
+ *                          The table (rt_srgb_thresholds, csrc/srgb_table.h, generated by
+ *                          tools/gen_srgb_table.py) is the definition: the frame agrees with
+ *                          it for every float32 input.
+ *   RT_FORMAT_RGBA16F 8 B  IEEE float32 -> float16, round to nearest even, all four
+ *                          channels; no clamp, overflow becomes inf, NaN stays NaN.
+ * Bytes in memory are R, G, B, A (a little-endian dword R | G<<8 | B<<16 | A<<24). The
+ * frame's alpha is exactly 1: 255, or 0x3C00 for RGBA16F. Rows are compact, as for
+ * RT_FORMAT_RGBA32F (row r of dst; there is no image-row variant). RGBA8 / SRGBA8:
+ * pitch >= 4*width, dst and pitch 4-byte aligned; RGBA16F: pitch >= 8*width, dst and pitch
+ * 8-byte aligned. Anything else, an unknown format included, is RT_ERR_INVALID before
+ * anything is launched. With rt_set_samples the stored pixel is the conversion of the
+ * float32 box-filtered value defined there. No tone mapping beyond the clamp, no dither. */
+enum rt_format {
+    RT_FORMAT_RGBA32F = 0, RT_FORMAT_RGB32F = 1, RT_FORMAT_RGBA32F_IMAGE = 2,
+    RT_FORMAT_RGBA8 = 3, RT_FORMAT_SRGBA8 = 4, RT_FORMAT_RGBA16F = 5
+};
 int rt_dispatch_rows_fmt(struct rt_ctx* ctx, int width, int height, int y0, int stripe, int step, int out_rows,
                          float* dst, size_t pitch, int format);
 
@@ -199,7 +226,7 @@ int rt_dispatch_rows_ex(struct rt_ctx* ctx, int width, int height, int y0, int s
  * n in {1, 2, 4, 8}; 1 (default) is today's frame. RT_ERR_INVALID for any other n.
  *
  * Applied at the next dispatch, and to every dispatch form (rt_dispatch, rt_dispatch_rows,
- * _fmt, _ex; all three formats, any y0 / stripe / period / out_rows). The caller's width,
+ * _fmt, _ex; every format, any y0 / stripe / period / out_rows). The caller's width,
  * height, rows, pitch and rt_params keep their meaning: they describe the OUTPUT frame.
  * The samples are the pixels of the one-sample frame with width, height, y0, stripe,
  * period, out_rows, resX and resY all multiplied by n (the reference's pixel NDC is
@@ -240,11 +267,32 @@ int rt_sync_frame(struct rt_ctx* ctx);
 
 /* Read the context surface back to host memory: `height` rows of `pitch` bytes.
  * width/height state the destination's size and must equal the surface's (the
- * last rt_dispatch's W x H), so a short buffer is refused, never overrun. */
+ * last rt_dispatch's W x H), so a short buffer is refused, never overrun.
+ * RT_ERR_INVALID when the surface is not RGBA32F (rt_set_surface_format): use
+ * rt_read_surface. */
 int rt_read_image(struct rt_ctx* ctx, float* host_dst, size_t pitch, int width, int height);
 
-/* Device pointer and pitch of the context surface (zero-copy hand-off). */
+/* Device pointer and pitch of the context surface (zero-copy hand-off), in the
+ * surface's format. */
 int rt_device_image(struct rt_ctx* ctx, void** ptr, size_t* pitch);
+
+/* The format of the context's own surface: RT_FORMAT_RGBA32F (default), RT_FORMAT_RGBA8,
+ * RT_FORMAT_SRGBA8 or RT_FORMAT_RGBA16F; any other value is RT_ERR_INVALID. Applies at the
+ * next rt_dispatch, which reallocates the surface (pitched at the format's row bytes,
+ * zero-filled) when the format, width or height changed; until then the surface, and what
+ * rt_read_image / rt_read_surface / rt_device_image see, stay as they are.
+ * rt_surface_format returns the format set here. */
+int rt_set_surface_format(struct rt_ctx* ctx, int format);
+int rt_surface_format(struct rt_ctx* ctx, int* format);
+
+/* rt_read_image for whatever format the surface has: `height` rows of `pitch` bytes,
+ * pitch >= bytes per pixel * width. width/height must equal the surface's, so a short
+ * buffer is refused, never overrun. A 1920x1080 RGBA8 frame is 8.3 MB against 33.2 MB. */
+int rt_read_surface(struct rt_ctx* ctx, void* host_dst, size_t pitch, int width, int height);
+
+/* The table T[1..255] that defines RT_FORMAT_SRGBA8, as 255 floats: out255[k - 1] = T[k].
+ * Needs no device. */
+int rt_srgb_thresholds(float* out255);
 
 /* Runs the counting variant of the reference traversal over the same rows as
  * rt_dispatch_rows and returns the totals (synchronous; not for timed loops). */

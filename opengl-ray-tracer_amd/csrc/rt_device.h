@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "srgb_table.h"
+
 namespace rtd {
 
 // ---------------------------------------------------------------------------
@@ -127,7 +129,8 @@ struct KParams {
     int tail_counters;                       // counters per set (>= tail_regions; all zeroed for the next)
     int tail_max_lanes;                      // a wave queues its rays only if at most this many are alive
     int rgb;                                 // output format (rt_dispatch_rows_fmt): 0 RGBA32F, 1 packed RGB32F
-                                             // (12 B per pixel), 2 RGBA32F at the image row (RT_FORMAT_RGBA32F_IMAGE)
+                                             // (12 B per pixel), 2 RGBA32F at the image row (RT_FORMAT_RGBA32F_IMAGE),
+                                             // 3 RGBA8, 4 SRGBA8, 5 RGBA16F (display formats, store_display)
     float shadow_off;                        // k_accel's shadow-ray offset: 1e-3 (BVH branch, gpu_shader.comp:469);
                                              // 1e-5 when it renders the brute branch (:565, rt_ctx::brute)
     int ss;                                  // rt_set_samples: 1, or n > 1 when the fields above describe the
@@ -312,8 +315,80 @@ __device__ __forceinline__ PrimRec load_prim(const float4* __restrict__ base, in
     return g;
 }
 
+// ---------------------------------------------------------------------------
+// Display formats (include/rt_api.h: RT_FORMAT_RGBA8 = 3, RT_FORMAT_SRGBA8 = 4,
+// RT_FORMAT_RGBA16F = 5): the float32 pixel converted in registers, one store.
+//
+// kSrgbT[k] = T[k] for k = 1..255 (srgb_table.h, the definition of SRGBA8), with
+// kSrgbT[0] = 0 and kSrgbT[256] = +inf, so a clamped channel c has the code q, the
+// count of k in 1..255 with c >= T[k], exactly when kSrgbT[q] <= c < kSrgbT[q + 1].
+// In global memory (1 KB, cache-resident): k_accel's LDS is taken by the lane stacks.
+__device__ const float kSrgbT[257] = {0.0f, RT_SRGB_THRESHOLDS __builtin_inff()};
+
+// clamp of rt_api.h: fminf(fmaxf(c, 0), 1); NaN gives 0 (fmaxf returns its other operand)
+__device__ __forceinline__ float clamp01(float c) { return fminf(fmaxf(c, 0.0f), 1.0f); }
+
+__device__ __forceinline__ unsigned unorm8(float c) {
+    return static_cast<unsigned>(static_cast<int>(rintf(clamp01(c) * 255.0f)));
+}
+
+// The SRGBA8 code of one channel. A guess from the closed form (v_log_f32 / v_exp_f32:
+// approximate, any error is allowed) is accepted when the two table entries around it
+// bracket c, which is the definition; otherwise a binary search over the table answers.
+// So the result agrees with the table for every float32 input, whatever the guess.
+__device__ __forceinline__ unsigned srgb8(float c) {
+    c = clamp01(c);
+    const float s = c <= 0.0031308f ? 12.92f * c : 1.055f * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(c) * (1.0f / 2.4f)) - 0.055f;
+    int q = static_cast<int>(fminf(fmaxf(s * 255.0f + 0.5f, 0.0f), 255.0f));
+    if (!(kSrgbT[q] <= c && c < kSrgbT[q + 1])) {
+        int lo = 0, hi = 256;  // kSrgbT[lo] <= c < kSrgbT[hi]
+#pragma unroll 1
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (c >= kSrgbT[mid]) lo = mid;
+            else hi = mid;
+        }
+        q = lo;
+    }
+    return static_cast<unsigned>(q);
+}
+
+__device__ __forceinline__ unsigned half_bits(float c) {
+    return __builtin_bit_cast(unsigned short, static_cast<_Float16>(c));  // v_cvt_f16_f32: nearest even, inf on overflow
+}
+
+// One display pixel at p (4 B for the 8-bit formats, 8 B for RGBA16F; aligned by
+// fill_kparams' checks), bytes R, G, B, A. Alpha is 255 / 0x3C00: the frame's is exactly 1.
+typedef unsigned rt_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void store_display(char* p, int format, float4 v) {
+    if (format == 5) {
+        rt_u32x2 h;
+        h.x = half_bits(v.x) | half_bits(v.y) << 16;
+        h.y = half_bits(v.z) | 0x3C000000u;
+        __builtin_nontemporal_store(h, reinterpret_cast<rt_u32x2*>(p));
+        return;
+    }
+    const unsigned w = format == 4 ? srgb8(v.x) | srgb8(v.y) << 8 | srgb8(v.z) << 16
+                                   : unorm8(v.x) | unorm8(v.y) << 8 | unorm8(v.z) << 16;
+    __builtin_nontemporal_store(w | 0xFF000000u, reinterpret_cast<unsigned*>(p));
+}
+__device__ __forceinline__ size_t display_bytes(int format) { return format == 5 ? 8 : 4; }
+
+// Which formats a kernel's store is compiled for. k_lane, k_packet and k_accel_tail take any
+// (one test of kp.rgb). k_accel has an instance of each kind: next to the float stores, the
+// conversion moved the register allocation of instances that sit at the 128-VGPR cap
+// (inlined, four gained scratch; as a call, twelve), though no float frame takes the branch.
+// So the float instances are compiled without it and are the code they were.
+enum StoreKind { kStoreFloat = 0, kStoreDisplay = 1, kStoreAny = 2 };
+
 // Writes the pixel for output row r, column x.
+template <int KIND = kStoreAny>
 __device__ __forceinline__ void store_px(const KParams& kp, int r, int x, float4 v) {
+    if (KIND == kStoreDisplay || (KIND == kStoreAny && kp.rgb >= 3)) {  // display formats: compact rows
+        store_display(kp.dst + static_cast<size_t>(r) * kp.pitch + static_cast<size_t>(x) * display_bytes(kp.rgb),
+                      kp.rgb, v);
+        return;
+    }
     if (kp.rgb == 1) {  // alpha is always 1 (gpu_shader.comp:437,623): the multi-GPU gather sends 12 B per pixel
         float* p = reinterpret_cast<float*>(kp.dst + static_cast<size_t>(r) * kp.pitch) + 3 * x;
         __builtin_nontemporal_store(v.x, p);
@@ -336,8 +411,15 @@ __device__ __forceinline__ void store_px(const KParams& kp, int r, int x, float4
 // The supersampling store (rt_set_samples, kp.ss = n > 1): the first lane of an n x n block
 // of sample pixels writes their mean to output row r / n, column x / n (sample row r,
 // column x; image_row of n * R + j is n * the output's image row + j).
+template <int KIND = kStoreAny>
 __device__ __forceinline__ void store_px_ss(const KParams& kp, int r, int x, float4 v) {
     const int sh = 31 - __builtin_clz(kp.ss);
+    if (KIND == kStoreDisplay || (KIND == kStoreAny && kp.rgb >= 3)) {
+        store_display(kp.dst + static_cast<size_t>(r >> sh) * kp.pitch +
+                          static_cast<size_t>(x >> sh) * display_bytes(kp.rgb),
+                      kp.rgb, v);
+        return;
+    }
     if (kp.rgb == 1) {
         float* p = reinterpret_cast<float*>(kp.dst + static_cast<size_t>(r >> sh) * kp.pitch) + 3 * (x >> sh);
         __builtin_nontemporal_store(v.x, p);

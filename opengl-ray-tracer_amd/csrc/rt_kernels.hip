@@ -1717,7 +1717,8 @@ __device__ __forceinline__ void bounce_step(const AccelPtrs& A, const float4* __
 // orders a later dispatch (rt_set_schedule). COUNT adds the per-walk records.
 // SS: a supersampled frame (rt_set_samples): kp describes the sample frame, and the store
 // writes the mean of each kp.ss x kp.ss block of lanes (store_px_ss) instead of every lane.
-template <bool COUNT, bool COST = true, bool TAIL = false, bool MT = false, bool QUEUE = TAIL, bool SS = false>
+template <bool COUNT, bool COST = true, bool TAIL = false, bool MT = false, bool QUEUE = TAIL, bool SS = false,
+          bool DISP = false>
 __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, const KParams& kp, int tile,
                            int part, int* stk, unsigned short* stt, int cap, WalkCount& wc,
                            unsigned long long* rec, bool heavy) {
@@ -1800,10 +1801,12 @@ __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, c
         const int lane = threadIdx.x & 63;
         const float w = 1.0f / static_cast<float>(kp.ss * kp.ss);  // a power of two: exact
         if (pc.active && mine && ((lane | lane >> 3) & (kp.ss - 1)) == 0)
-            store_px_ss(kp, pc.r, pc.x, make_float4(acc.x * w, acc.y * w, acc.z * w, 1.0f));
+            store_px_ss<DISP ? kStoreDisplay : kStoreFloat>(kp, pc.r, pc.x,
+                                                            make_float4(acc.x * w, acc.y * w, acc.z * w, 1.0f));
         return;
     }
-    if (pc.active && mine && !deferred) store_px(kp, pc.r, pc.x, make_float4(acc.x, acc.y, acc.z, 1.0f));
+    if (pc.active && mine && !deferred)
+        store_px<DISP ? kStoreDisplay : kStoreFloat>(kp, pc.r, pc.x, make_float4(acc.x, acc.y, acc.z, 1.0f));
 }
 
 // One dispatch slot per wave. TIMED writes each tile's start/end wall clock and
@@ -1818,8 +1821,10 @@ __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, c
 // TAIL: queue the rays alive after bounce tail_from - 1 for k_accel_tail (rt_set_tail).
 // SS: the supersampling instances (rt_set_samples): the same tiles over the sample frame,
 // each n x n block of lanes stored as one mean pixel (accel_tile).
+// DISP: the instance's twin for the display formats (RT_FORMAT_RGBA8, SRGBA8, RGBA16F: StoreKind
+// in rt_device.h); launch() takes it from kAccelTwins.
 template <bool TIMED, bool COST = true, bool TAIL = false, bool MT = false, bool REC = COST, bool QUEUE = TAIL,
-          bool SS = false>
+          bool SS = false, bool DISP = false>
 __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, const float4* __restrict__ mat, KParams kp) {
     extern __shared__ int lds_stack[];
     // per-lane stacks, entry j of lane i at [j * blockDim.x + i]: codes, then bf16 entry parameters
@@ -1852,8 +1857,8 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, con
         // a split tile's parts stamp records tiles + slot (rt_debug_tile_times with room for them)
         unsigned long long* rec =
             TIMED ? kp.tile_times + kTileRec * static_cast<size_t>(part > 0 ? kp.tiles + slot : tile) : nullptr;
-        accel_tile<TIMED, COST, TAIL, MT, QUEUE, SS>(A, mat, kp, tile, part, stk, stt, kp.lane_stack, wc, rec,
-                                                     slot < kp.lane_k);
+        accel_tile<TIMED, COST, TAIL, MT, QUEUE, SS, DISP>(A, mat, kp, tile, part, stk, stt, kp.lane_stack, wc, rec,
+                                                           slot < kp.lane_k);
         if (TIMED) {
             const unsigned long long t1 = wall_clock64();
             unsigned long long sn = wc.nodes, st = wc.tests, mn = wc.nodes, mt = wc.tests;
@@ -1912,6 +1917,28 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, con
         }
     }
 }
+
+// Every k_accel instance launch() can choose, <TIMED, COST, TAIL, MT, REC, QUEUE, SS>, with
+// its twin for the display formats (DISP).
+#define RT_ACCEL_INSTANCES(X)                                                                    \
+    X(false, false, false, false, false, false, false) X(false, false, false, false, false, false, true) \
+    X(false, false, false, false, true, false, false) X(false, false, false, false, true, false, true)   \
+    X(false, false, false, true, false, false, false) X(false, false, false, true, false, false, true)   \
+    X(false, false, false, true, true, false, false) X(false, false, false, true, true, false, true)     \
+    X(false, false, true, false, false, false, false) X(false, false, true, false, false, false, true)   \
+    X(false, false, true, false, false, true, false) X(false, false, true, false, true, false, false)    \
+    X(false, false, true, false, true, false, true) X(false, false, true, false, true, true, false)      \
+    X(false, true, false, false, true, false, false) X(false, true, false, false, true, false, true)     \
+    X(false, true, false, true, true, false, false) X(false, true, false, true, true, false, true)       \
+    X(false, true, true, false, true, false, false) X(false, true, true, false, true, false, true)       \
+    X(false, true, true, false, true, true, false) X(true, true, false, false, true, false, false)
+struct AccelTwin {
+    void (*plain)(AccelPtrs, const float4*, KParams);
+    void (*display)(AccelPtrs, const float4*, KParams);
+};
+#define RT_ACCEL_TWIN(...) {k_accel<__VA_ARGS__>, k_accel<__VA_ARGS__, true>},
+const AccelTwin kAccelTwins[] = {RT_ACCEL_INSTANCES(RT_ACCEL_TWIN)};
+#undef RT_ACCEL_TWIN
 
 // The queued rays' remaining bounces (rt_set_tail): one wave per possible chunk
 // of 64 rays (kTailRegion / 64 per region), each taking one. The same bounce arithmetic as
@@ -2121,7 +2148,9 @@ __device__ __forceinline__ float4 box_y(const char* __restrict__ p, size_t pitch
     }
 }
 // width, height, y0, stripe, period, out_rows: the OUTPUT frame's (rt_dispatch_rows_ex).
-template <int N>
+// DISP: the instance for the display formats (kept apart: with both stores in one kernel
+// k_box_filter<8> went from 76 to 256 VGPRs).
+template <int N, bool DISP = false>
 __global__ __launch_bounds__(256) void k_box_filter(const char* __restrict__ src, size_t src_pitch,
                                                     char* __restrict__ dst, size_t pitch, int width, int height,
                                                     int y0, int stripe, int period, int out_rows, int format) {
@@ -2134,6 +2163,10 @@ __global__ __launch_bounds__(256) void k_box_filter(const char* __restrict__ src
                            src_pitch);
     const float w = 1.0f / static_cast<float>(N * N);
     v = make_float4(v.x * w, v.y * w, v.z * w, v.w * w);
+    if (DISP) {  // display formats: the conversion of the filtered float32 value
+        store_display(dst + static_cast<size_t>(r) * pitch + static_cast<size_t>(x) * display_bytes(format), format, v);
+        return;
+    }
     if (format == RT_FORMAT_RGB32F) {
         float* p = reinterpret_cast<float*>(dst + static_cast<size_t>(r) * pitch) + 3 * x;
         p[0] = v.x;
@@ -2986,12 +3019,15 @@ struct rt_ctx {
     float* img = nullptr;
     size_t img_pitch = 0;
     int img_w = 0, img_h = 0;
+    int img_fmt = RT_FORMAT_RGBA32F;   // the allocated surface's format
+    int surf_fmt = RT_FORMAT_RGBA32F;  // rt_set_surface_format: the next rt_dispatch's
     // rt_set_samples: n x n samples per pixel. Frames k_accel renders reduce them in its
     // store (the SS instances); every other frame renders the sample frame into ss_buf
     // (compact rows, RGBA32F; kept between frames, reallocated when the size changes) and
     // k_box_filter writes the output. ss_general: rt_debug_ss_general forces the latter.
     int samples = 1;
     bool ss_general = false;
+    bool convert_pass = false;  // rt_debug_convert_pass
     char* ss_buf = nullptr;
     size_t ss_bytes = 0;
     unsigned long long* stats_dev = nullptr;
@@ -4344,15 +4380,33 @@ void fill_camera(const FlatCamera& cam, KParams& kp) {
     kp.plane_w = h * cam.aspectRatio;
 }
 
+// Bytes per pixel of an rt_format (0: not a format) and the alignment of its dst and pitch:
+// a pixel is one store of 16 B (RGBA32F), three of 4 B (RGB32F), one of 4 B (the 8-bit
+// formats) or one of 8 B (RGBA16F).
+size_t format_bytes(int format) {
+    switch (format) {
+        case RT_FORMAT_RGBA32F:
+        case RT_FORMAT_RGBA32F_IMAGE: return 16;
+        case RT_FORMAT_RGB32F: return 12;
+        case RT_FORMAT_RGBA8:
+        case RT_FORMAT_SRGBA8: return 4;
+        case RT_FORMAT_RGBA16F: return 8;
+        default: return 0;
+    }
+}
+size_t format_align(int format) {
+    const size_t px = format_bytes(format);
+    return px == 12 || px == 0 ? 4 : px;
+}
+
 // ss > 1 (rt_set_samples): width .. out_rows are the SAMPLE frame's, ss times the output
 // frame's that dst, pitch and format describe (KParams::ss); resX, resY are scaled to match.
 int fill_kparams(rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows, float* dst,
                  size_t pitch, KParams& kp, int format = RT_FORMAT_RGBA32F, int ss = 1) {
     if (!c->have_scene || !c->have_cam || !c->have_light) return RT_ERR_NO_SCENE;
-    const size_t px = format == RT_FORMAT_RGB32F ? 12 : 16, align = format == RT_FORMAT_RGB32F ? 4 : 16;
+    const size_t px = format_bytes(format), align = format_align(format);
     if (width <= 0 || height <= 0 || stripe <= 0 || period < stripe || out_rows < 0 || y0 < 0 || !dst ||
-        (format != RT_FORMAT_RGBA32F && format != RT_FORMAT_RGB32F && format != RT_FORMAT_RGBA32F_IMAGE) ||
-        ss < 1 || pitch < static_cast<size_t>(width / ss) * px ||
+        px == 0 || ss < 1 || pitch < static_cast<size_t>(width / ss) * px ||
         (pitch % align) != 0 || (reinterpret_cast<uintptr_t>(dst) % align) != 0)
         return RT_ERR_INVALID;
     std::memset(&kp, 0, sizeof kp);
@@ -4383,7 +4437,7 @@ int fill_kparams(rt_ctx* c, int width, int height, int y0, int stripe, int perio
     kp.dst = reinterpret_cast<char*>(dst);
     kp.pitch = pitch;
     kp.shadow_off = 1e-3f;
-    kp.rgb = format;  // RT_FORMAT_*: 0 RGBA32F, 1 RGB32F, 2 RGBA32F at the image row
+    kp.rgb = format;  // RT_FORMAT_*: 0 RGBA32F, 1 RGB32F, 2 RGBA32F at the image row, 3-5 display formats
     kp.heavy_k = 0;
     kp.heavy_parts = 1;
     kp.lane_k = 0;
@@ -4452,6 +4506,7 @@ void inherit(rt_ctx* b, const rt_ctx* c) {
     b->scene_stack = c->scene_stack;
     b->lane_stack_override = c->lane_stack_override;
     b->ss_general = c->ss_general;
+    b->convert_pass = c->convert_pass;
 }
 
 // The walk policy in force (rt_set_walk, or auto): barycentric frames walk camera
@@ -4600,6 +4655,11 @@ int render_frame(rt_ctx* c, const KParams& kp, rt_ctx** from) {
 void launch_box_filter(rt_ctx* c, const KParams& out) {
     const int n = out.ss, w = out.width / n, rows = out.out_rows / n;
     auto kfn = n == 2 ? k_box_filter<2> : n == 4 ? k_box_filter<4> : k_box_filter<8>;
+    if (out.rgb >= RT_FORMAT_RGBA8)  // n == 1: the conversion alone (rt_debug_convert_pass)
+        kfn = n == 1   ? k_box_filter<1, true>
+              : n == 2 ? k_box_filter<2, true>
+              : n == 4 ? k_box_filter<4, true>
+                       : k_box_filter<8, true>;
     hipLaunchKernelGGL(kfn, dim3((w + 63) / 64, (rows + 3) / 4), dim3(256), 0, c->stream, c->ss_buf,
                        static_cast<size_t>(out.width) * sizeof(float4), out.dst, out.pitch, w, out.height / n,
                        out.y0 / n, out.stripe / n, out.period / n, rows, out.rgb);
@@ -4621,8 +4681,11 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
     // the context's scratch surface, then k_box_filter (general).
     const bool ss = !stats && kin.ss > 1;
     const bool ss_fused = ss && kind == RT_KERNEL_ACCEL && !c->tile_times && !c->ss_general;
+    // rt_debug_convert_pass: a one-sample display frame the same way, float frame first, then
+    // the filter kernel's conversion (the measurement's baseline, tools/bench_formats.py)
+    const bool filter = ss ? !ss_fused : !stats && c->convert_pass && kin.rgb >= RT_FORMAT_RGBA8;
     KParams kp = kin;
-    if (ss && !ss_fused) {
+    if (filter) {
         const size_t spitch = static_cast<size_t>(kin.width) * sizeof(float4);
         const size_t need = spitch * static_cast<size_t>(kin.out_rows);
         if (need != c->ss_bytes) {
@@ -4653,7 +4716,7 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
     } else if (kind == RT_KERNEL_LANE) {
         hipLaunchKernelGGL(k_lane<false>, grid, dim3(kBlock), lds, c->stream, c->geo_leaf, c->geo_lin, c->mat,
                            c->nodes, kp);
-        if (ss) launch_box_filter(c, kin);
+        if (filter) launch_box_filter(c, kin);
     } else if (kind == RT_KERNEL_ACCEL) {
         KParams k2 = kp;
         k2.tiles_x = (kp.width + 7) / 8;
@@ -4930,6 +4993,14 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
                       : k2.cost_time ? k_accel<false, false, false, false, true, false, true>
                                      : k_accel<false, true, false, false, true, false, true>;
         }
+        if (k2.rgb >= RT_FORMAT_RGBA8) {
+            // a display format: the chosen instance's twin, compiled with the conversion
+            auto twin = decltype(kfn){nullptr};
+            for (const AccelTwin& t : kAccelTwins)
+                if (t.plain == kfn) twin = t.display;
+            if (!twin) return RT_ERR_INVALID;  // an instance without a twin: kAccelTwins is out of date
+            kfn = twin;
+        }
         const bool tail_on = k2.tail_queue != nullptr;
         // one wave per dispatch slot: the split heavy tiles' extra waves too
         const int blocks = k2.tiles + k2.heavy_k * (k2.heavy_parts - 1);
@@ -4940,7 +5011,7 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
             hipLaunchKernelGGL(k_accel_tail, dim3(tgrid), dim3(64), tlds, c->stream, A, c->mat, k2);
             c->tail_parity = 1 - c->tail_parity;
         }
-        if (ss && !ss_fused) launch_box_filter(c, kin);
+        if (filter) launch_box_filter(c, kin);
         if (k2.tile_cost) {
             // the next frame's order; stream-ordered after this dispatch (and after its
             // end event, so rt_kernel_times is the render kernel alone), before the next
@@ -4982,7 +5053,7 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
     } else {
         hipLaunchKernelGGL(k_packet, grid, dim3(kBlock), 0, c->stream, c->geo_leaf, c->geo_lin, c->mat, c->nodes,
                            kp);
-        if (ss) launch_box_filter(c, kin);
+        if (filter) launch_box_filter(c, kin);
     }
     c->last_kind = stats ? RT_KERNEL_LANE : kind;
     HIP_TRY(hipGetLastError());
@@ -5638,23 +5709,45 @@ int rt_set_samples(rt_ctx* c, int n) {
 int rt_dispatch(rt_ctx* c, int width, int height, int y0, int y1) {
     if (!c || width <= 0 || height <= 0 || y0 < 0 || y1 > height || y0 > y1) return RT_ERR_INVALID;
     if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
-    if (width != c->img_w || height != c->img_h || !c->img) {
+    if (width != c->img_w || height != c->img_h || c->surf_fmt != c->img_fmt || !c->img) {
         HIP_TRY(sync_stream(c));
         hipFree(c->img);
         c->img = nullptr;
         c->img_w = c->img_h = 0;
         size_t pitch = 0;
-        if (hipMallocPitch(reinterpret_cast<void**>(&c->img), &pitch, static_cast<size_t>(width) * 16, height) !=
-            hipSuccess)
+        const size_t row = static_cast<size_t>(width) * format_bytes(c->surf_fmt);
+        if (hipMallocPitch(reinterpret_cast<void**>(&c->img), &pitch, row, height) != hipSuccess)
             return RT_ERR_NO_MEMORY;
-        HIP_TRY(hipMemset2DAsync(c->img, pitch, 0, static_cast<size_t>(width) * 16, height, c->stream));
+        HIP_TRY(hipMemset2DAsync(c->img, pitch, 0, row, height, c->stream));
         c->img_pitch = pitch;
         c->img_w = width;
         c->img_h = height;
+        c->img_fmt = c->surf_fmt;
     }
-    return rt_dispatch_rows(c, width, height, y0, 1, 1, y1 - y0,
-                            reinterpret_cast<float*>(reinterpret_cast<char*>(c->img) + y0 * c->img_pitch),
-                            c->img_pitch);
+    return rt_dispatch_rows_fmt(c, width, height, y0, 1, 1, y1 - y0,
+                                reinterpret_cast<float*>(reinterpret_cast<char*>(c->img) + y0 * c->img_pitch),
+                                c->img_pitch, c->img_fmt);
+}
+
+int rt_set_surface_format(rt_ctx* c, int format) {
+    if (!c || (format != RT_FORMAT_RGBA32F && format != RT_FORMAT_RGBA8 && format != RT_FORMAT_SRGBA8 &&
+               format != RT_FORMAT_RGBA16F))
+        return RT_ERR_INVALID;
+    c->surf_fmt = format;
+    return RT_OK;
+}
+
+int rt_surface_format(rt_ctx* c, int* format) {
+    if (!c || !format) return RT_ERR_INVALID;
+    *format = c->surf_fmt;
+    return RT_OK;
+}
+
+int rt_srgb_thresholds(float* out255) {
+    static const float t[255] = {RT_SRGB_THRESHOLDS};
+    if (!out255) return RT_ERR_INVALID;
+    std::memcpy(out255, t, sizeof t);
+    return RT_OK;
 }
 
 int rt_sync(rt_ctx* c) {
@@ -5706,15 +5799,19 @@ int rt_sync_frame(rt_ctx* c) {
     return RT_OK;
 }
 
-int rt_read_image(rt_ctx* c, float* dst, size_t pitch, int width, int height) {
-    if (!c || !dst || !c->img || width != c->img_w || height != c->img_h ||
-        pitch < static_cast<size_t>(c->img_w) * 16)
-        return RT_ERR_INVALID;
+int rt_read_surface(rt_ctx* c, void* dst, size_t pitch, int width, int height) {
+    if (!c || !dst || !c->img || width != c->img_w || height != c->img_h) return RT_ERR_INVALID;
+    const size_t row = static_cast<size_t>(c->img_w) * format_bytes(c->img_fmt);
+    if (pitch < row) return RT_ERR_INVALID;
     if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
-    HIP_TRY(hipMemcpy2DAsync(dst, pitch, c->img, c->img_pitch, static_cast<size_t>(c->img_w) * 16, c->img_h,
-                             hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(dst, pitch, c->img, c->img_pitch, row, c->img_h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(sync_stream(c));
     return RT_OK;
+}
+
+int rt_read_image(rt_ctx* c, float* dst, size_t pitch, int width, int height) {
+    if (!c || c->img_fmt != RT_FORMAT_RGBA32F) return RT_ERR_INVALID;
+    return rt_read_surface(c, dst, pitch, width, height);
 }
 
 int rt_device_image(rt_ctx* c, void** p, size_t* pitch) {
@@ -6160,6 +6257,37 @@ extern "C" int rt_debug_split(rt_ctx* c, int max_rays, int group) {
 // Diagnostics: supersampled frames (rt_set_samples) take the general path -- the sample
 // frame into the scratch surface, then k_box_filter -- even where k_accel would reduce the
 // samples in its store. Same image either way (tests, tools/bench_ss.py's baseline).
+// Diagnostics: frames in a display format render as a float frame into the scratch surface
+// followed by the filter kernel's conversion, instead of converting in the render kernel's
+// store. Same image either way (tools/bench_formats.py's baseline).
+extern "C" int rt_debug_convert_pass(rt_ctx* c, int on) {
+    if (!c) return RT_ERR_INVALID;
+    c->convert_pass = on != 0;
+    return RT_OK;
+}
+
+// Diagnostics: the display conversion alone over caller data, so that tests can feed it values
+// no frame holds (NaN, infinities, ties, the sRGB thresholds and their neighbours): `rows` compact
+// rows of `width` RGBA32F pixels at device pointer src become rows of `format` at dst, by the
+// filter kernel's conversion (the render kernels' store_display). Stream-ordered, asynchronous.
+extern "C" int rt_debug_convert(rt_ctx* c, const float* src, size_t src_pitch, void* dst, size_t pitch, int width,
+                                int rows, int format) {
+    if (!c || !src || !dst || width <= 0 || rows <= 0 || rows > 4 * 65535 || format < RT_FORMAT_RGBA8 ||
+        format_bytes(format) == 0)
+        return RT_ERR_INVALID;
+    const size_t px = format_bytes(format), align = format_align(format);
+    if (src_pitch < static_cast<size_t>(width) * 16 || src_pitch % 16 != 0 ||
+        reinterpret_cast<uintptr_t>(src) % 16 != 0 || pitch < static_cast<size_t>(width) * px || pitch % align != 0 ||
+        reinterpret_cast<uintptr_t>(dst) % align != 0)
+        return RT_ERR_INVALID;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    hipLaunchKernelGGL((k_box_filter<1, true>), dim3((width + 63) / 64, (rows + 3) / 4), dim3(256), 0, c->stream,
+                       reinterpret_cast<const char*>(src), src_pitch, static_cast<char*>(dst), pitch, width, rows, 0, 1,
+                       1, rows, format);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
 extern "C" int rt_debug_ss_general(rt_ctx* c, int on) {
     if (!c) return RT_ERR_INVALID;
     c->ss_general = on != 0;

@@ -221,6 +221,9 @@ RT_SYMBOLS = {
     "rt_dispatch_rows_ex": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _I]),
     "rt_sync": (_I, [_P]), "rt_sync_frame": (_I, [_P]), "rt_read_image": (_I, [_P, _P, C.c_size_t, _I, _I]),
     "rt_device_image": (_I, [_P, _P, _P]),
+    "rt_set_surface_format": (_I, [_P, _I]), "rt_surface_format": (_I, [_P, _P]),
+    "rt_read_surface": (_I, [_P, _P, C.c_size_t, _I, _I]),
+    "rt_srgb_thresholds": (_I, [_P]),
     "rt_collect_stats": (_I, [_P, _I, _I, _I, _I, _I, _I, _P]),
     "rt_collect_stats_ex": (_I, [_P, _I, _I, _I, _I, _I, _I, _P]),
     "rt_last_kernel_ms": (_I, [_P, _P]),
@@ -274,6 +277,10 @@ GROUP_SYMBOLS = {
 }
 GATHER_AUTO, GATHER_RCCL, GATHER_COPY = 0, 1, 2
 FORMAT_RGBA32F, FORMAT_RGB32F, FORMAT_RGBA32F_IMAGE = 0, 1, 2  # rt_format
+FORMAT_RGBA8, FORMAT_SRGBA8, FORMAT_RGBA16F = 3, 4, 5  # rt_format: the display formats
+# bytes per pixel and the numpy type of one channel, for the formats a context surface can have
+SURFACE_DTYPE = {FORMAT_RGBA32F: np.float32, FORMAT_RGBA8: np.uint8, FORMAT_SRGBA8: np.uint8,
+                 FORMAT_RGBA16F: np.float16}
 GROUP_ID_BYTES = 128
 
 
@@ -556,6 +563,16 @@ def write_image(path, img, fmt=IMAGE_PPM):
         raise RTError("rts_write_image", rc)
 
 
+def srgb_thresholds():
+    """rt_srgb_thresholds: the 255 float32 thresholds T[1..255] that define FORMAT_SRGBA8
+    (result[k - 1] = T[k]): a channel c encodes to the count of k with clamp(c, 0, 1) >= T[k]."""
+    out = np.zeros(255, np.float32)
+    rc = rt_lib().rt_srgb_thresholds(_ptr(out))
+    if rc != 0:
+        raise RTError("rt_srgb_thresholds", rc)
+    return out
+
+
 def generate(config, variant=0, width=1920, height=1080) -> FlatScene:
     """One of the BASELINE configurations as serialised arrays."""
     sc = Scene().generate(config, variant, float(width) / float(height))
@@ -674,11 +691,47 @@ class ComputeShader:
         self._chk(self._lib.rt_read_image(self._h, _ptr(out), width * 16, width, height), "rt_read_image")
         return out
 
-    def render(self, width, height, y0=0, y1=None):
-        """dispatch + barrier + readback of the full surface."""
+    def set_surface_format(self, fmt):
+        """rt_set_surface_format: the context surface's format from the next dispatch on
+        (FORMAT_RGBA32F, FORMAT_RGBA8, FORMAT_SRGBA8 or FORMAT_RGBA16F)."""
+        self._chk(self._lib.rt_set_surface_format(self._h, int(fmt)), "rt_set_surface_format")
+        self._surface_fmt = int(fmt)  # render() reads floats through rt_read_image while this is RGBA32F
+
+    def surface_format(self):
+        f = C.c_int()
+        self._chk(self._lib.rt_surface_format(self._h, C.byref(f)), "rt_surface_format")
+        return f.value
+
+    def device_image(self):
+        """(pointer, pitch in bytes) of the context surface, in its format (rt_device_image)."""
+        p, pitch = C.c_void_p(), C.c_size_t()
+        self._chk(self._lib.rt_device_image(self._h, C.byref(p), C.byref(pitch)), "rt_device_image")
+        return p.value, pitch.value
+
+    def read_surface(self, width, height, out=None):
+        """rt_read_surface: the surface in the format set: [H, W, 4] uint8 (RGBA8, SRGBA8),
+        float16 (RGBA16F) or float32. out: a C-contiguous [H, W, 4] array of that type to
+        fill (pinned memory, say) instead of a new one."""
+        dt = np.dtype(SURFACE_DTYPE[self.surface_format()])
+        if out is None:
+            out = np.empty((height, width, 4), dt)
+        elif out.dtype != dt or out.shape != (height, width, 4) or not out.flags.c_contiguous:
+            raise ValueError(f"read_surface: out must be a C-contiguous [{height}, {width}, 4] {dt} array")
+        self._chk(self._lib.rt_read_surface(self._h, _ptr(out), width * 4 * dt.itemsize, width, height),
+                  "rt_read_surface")
+        return out
+
+    def render(self, width, height, y0=0, y1=None, fmt=None):
+        """dispatch + barrier + readback of the full surface. fmt: render and return the frame
+        in this surface format (set_surface_format; it stays set), float32 RGBA when None and
+        no other format is set."""
+        if fmt is not None:
+            self.set_surface_format(fmt)
         self.dispatch(width, height, y0, y1)
         self.sync()
-        return self.read_image(width, height)
+        if getattr(self, "_surface_fmt", FORMAT_RGBA32F) == FORMAT_RGBA32F:
+            return self.read_image(width, height)
+        return self.read_surface(width, height)
 
     def collect_stats(self, width, height, y0=0, stripe=1, step=1, out_rows=None):
         st = rt_stats()
@@ -774,6 +827,21 @@ class ComputeShader:
         fn = self._lib.rt_debug_ss_general
         fn.argtypes = [_P, _I]
         self._chk(fn(self._h, int(bool(on))), "rt_debug_ss_general")
+
+    def debug_convert_pass(self, on):
+        """Diagnostics: display-format frames render as a float frame followed by a conversion
+        kernel instead of converting in the render kernel's store (tools/bench_formats.py)."""
+        fn = self._lib.rt_debug_convert_pass
+        fn.argtypes = [_P, _I]
+        self._chk(fn(self._h, int(bool(on))), "rt_debug_convert_pass")
+
+    def debug_convert(self, src_ptr, src_pitch, dst_ptr, pitch, width, rows, fmt):
+        """Diagnostics: the display conversion alone: rows x width RGBA32F pixels at device pointer
+        src_ptr become pixels of display format fmt at dst_ptr (stream-ordered, asynchronous)."""
+        fn = self._lib.rt_debug_convert
+        fn.argtypes = [_P, _P, C.c_size_t, _P, C.c_size_t, _I, _I, _I]
+        self._chk(fn(self._h, C.c_void_p(src_ptr), src_pitch, C.c_void_p(dst_ptr), pitch, int(width), int(rows),
+                     int(fmt)), "rt_debug_convert")
 
     def debug_shadow_walk(self, from_bounce):
         fn = self._lib.rt_debug_shadow_walk
