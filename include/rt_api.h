@@ -254,6 +254,53 @@ int rt_dispatch_rows_ex(struct rt_ctx* ctx, int width, int height, int y0, int s
  * times n. Group frames (rt_group.h) stay one sample per pixel. */
 int rt_set_samples(struct rt_ctx* ctx, int n);
 
+/* Adaptive supersampling: with rt_set_samples n > 1, take the n x n samples only where
+ * neighbouring pixels of the one-sample frame disagree.
+ *
+ * threshold < 0 (default -1): off. threshold >= 0 (+inf allowed): on. NaN: RT_ERR_INVALID,
+ * and the previous setting stays. Applies at the next dispatch, to every dispatch form and
+ * format, when rt_set_samples n > 1; with n == 1 it changes nothing.
+ *
+ * Two frames define the result, both float32, before any format conversion:
+ *   B  the frame this dispatch would write with rt_set_samples(1);
+ *   S  the frame it would write with rt_set_samples(n) and adaptive off;
+ * over the dispatch's own pixels: compact rows r in [0, out_rows) whose image row y(r) is
+ * below height, and x in [0, width).
+ *
+ * Neighbours of (r, x): (r, x +- 1) where that x is inside the frame, and (r +- 1, x) where
+ * that compact row is one of the dispatch's own pixels and its image row is exactly
+ * y(r) +- 1. So a full frame has the usual 4-neighbourhood, and a stripe's first and last
+ * rows have no neighbour across the gap to the next stripe.
+ *
+ * A pixel p is refined iff, for some neighbour q and some channel c of R, G, B,
+ * !(fabsf(B(p).c - B(q).c) <= threshold), the subtraction being one float32 operation. A NaN
+ * therefore refines, and both pixels of a contrasting pair refine. Each pixel is S(p) if
+ * refined and B(p) otherwise, then goes through the dispatch's format conversion as ever;
+ * alpha is exactly 1. So every pixel holds one of two values the renderer already defines,
+ * and the threshold only decides which: +inf gives B exactly, a threshold below every
+ * contrast gives S exactly. (B(p) is also sample (0, 0) of p's block.)
+ *
+ * Limit: a feature thinner than a pixel between two pixels of equal colour is not found.
+ *
+ * Frames the accelerated kernel renders take the fast path: B as an ordinary one-sample
+ * dispatch (latency mode, cost order and rt_set_tail apply to it) into a surface the context
+ * keeps, one small kernel that writes the unrefined pixels and lists the refined ones, and
+ * one that shades the listed pixels' samples; the host reads nothing in between, the dispatch
+ * stays asynchronous. Every other frame (RT_KERNEL_LANE, RT_KERNEL_PACKET, no usable
+ * accelerator, a far camera) renders the whole sample frame as for rt_set_samples and picks
+ * per pixel in the filter kernel: the same image, exact for every kernel variant, and not
+ * faster than full supersampling.
+ *
+ * rt_collect_stats*, rt_trace_*, rt_group frames, the cost order and
+ * rt_accel_info::last_kernel (the kernel that rendered B) are unaffected. One rt_kernel_times
+ * entry covers all passes of the dispatch, and rt_sync_frame's marker follows the last. */
+int rt_set_adaptive(struct rt_ctx* ctx, float threshold);
+
+/* Pixels of the last dispatch that ran adaptively: how many were refined, how many it wrote
+ * (either pointer may be NULL). Waits for that dispatch. RT_ERR_INVALID if no dispatch of
+ * this context ran adaptively. */
+int rt_adaptive_stats(struct rt_ctx* ctx, uint64_t* refined, uint64_t* pixels);
+
 /* glMemoryBarrier + wait: blocks until the context's stream is drained. */
 int rt_sync(struct rt_ctx* ctx);
 

@@ -31,6 +31,10 @@
 //       N x N box filter of a sample frame the kernels above rendered.
 //   k_accel_tail    : the remaining bounces of the rays k_accel queued
 //       (rt_set_tail), 64 rays from one screen region to a wave.
+//   k_adaptive_classify / k_accel_refine<MT, DISP> / k_box_filter_adaptive<N, DISP> :
+//       adaptive supersampling (rt_set_adaptive): the pixels of the one-sample frame that
+//       contrast with a neighbour are listed and only their n x n samples shaded, or, for
+//       the frames k_accel does not render, picked from the whole sample frame.
 //   k_trace<MODE, MT> / k_trace_ref<MODE> : ray queries (rt_trace_rays, rt_trace_pixels):
 //       the caller's rays, or the camera rays of the caller's pixels, one per lane
 //       through lane_walk over the accelerator (k_trace) or through k_lane's literal
@@ -2178,6 +2182,192 @@ __global__ __launch_bounds__(256) void k_box_filter(const char* __restrict__ src
     reinterpret_cast<float4*>(dst + static_cast<size_t>(row) * pitch)[x] = v;
 }
 
+// ---------------------------------------------------------------------------
+// Adaptive supersampling (rt_set_adaptive, include/rt_api.h): B is the dispatch's one-sample
+// frame, S its n x n frame; a pixel takes S where B contrasts with a 4-neighbour and B
+// elsewhere. Frames k_accel renders (launch(), fast path): B into the context's scratch
+// surface by the ordinary one-sample dispatch, then
+//   k_adaptive_classify : one thread per output pixel writes the unrefined pixels and lists
+//                         the refined ones (one atomic per wave);
+//   k_accel_refine      : one wave per 64 / n^2 listed pixels shades their samples, per-lane
+//                         walks with k_accel_tail's LDS stacks, and stores the block means.
+// Every other frame (general path): the whole sample frame as for rt_set_samples, then
+// k_box_filter_adaptive picks the corner sample or the box mean per pixel -- exact for every
+// kernel variant, and no faster than full supersampling.
+
+// The rule on one pair of pixels: one float32 subtraction per channel; a NaN refines.
+__device__ __forceinline__ bool ad_contrast(float4 a, float4 b, float t) {
+    return !(fabsf(a.x - b.x) <= t) || !(fabsf(a.y - b.y) <= t) || !(fabsf(a.z - b.z) <= t);
+}
+
+// The OUTPUT frame's row mapping (rt_dispatch_rows_ex).
+struct AdRows {
+    int height, y0, stripe, period, out_rows;
+};
+__device__ __forceinline__ int ad_image_row(const AdRows& m, int r) {
+    return m.y0 + r + (r / m.stripe) * (m.period - m.stripe);
+}
+// Compact row r2 is one of the dispatch's own pixels' and lies at image row y.
+__device__ __forceinline__ bool ad_own_row(const AdRows& m, int r2, int y) {
+    return r2 >= 0 && r2 < m.out_rows && y < m.height && ad_image_row(m, r2) == y;
+}
+
+// Whether pixel (r, x) at image row y, of value p, is refined; px(r, x) reads B. Rows are
+// read only where ad_own_row holds, so nothing outside the dispatch's own pixels is touched.
+template <class Px>
+__device__ __forceinline__ bool ad_refines(const AdRows& m, int width, int r, int x, int y, float thr, float4 p,
+                                           Px px) {
+    bool ref = false;
+    if (x > 0) ref = ref || ad_contrast(p, px(r, x - 1), thr);
+    if (x + 1 < width) ref = ref || ad_contrast(p, px(r, x + 1), thr);
+    if (ad_own_row(m, r - 1, y - 1)) ref = ref || ad_contrast(p, px(r - 1, x), thr);
+    if (ad_own_row(m, r + 1, y + 1)) ref = ref || ad_contrast(p, px(r + 1, x), thr);
+    return ref;
+}
+
+// Adds the wave's refined pixels (ballot m, non-zero) to *count with one atomic; returns
+// this lane's position among them.
+__device__ __forceinline__ unsigned ad_append(unsigned* count, unsigned long long m) {
+    const int lane = threadIdx.x & 63;
+    unsigned base = 0;
+    if (lane == __builtin_ctzll(m)) base = atomicAdd(count, static_cast<unsigned>(__popcll(m)));
+    base = static_cast<unsigned>(__shfl(static_cast<int>(base), __builtin_ctzll(m)));
+    return base + static_cast<unsigned>(__popcll(m & ((1ull << lane) - 1ull)));
+}
+
+// kp: the one-sample OUTPUT frame with the dispatch's dst, pitch and format; k_lane's grid,
+// so a wave is an 8x8 tile and the list stays coherent tile by tile. bsrc: B, compact rows
+// of RGBA32F. list: r * width + x per refined pixel (unsigned: launch() keeps it below
+// 2^32), capacity out_rows * width; *count: zeroed in stream order before this kernel.
+__global__ __launch_bounds__(kBlock) void k_adaptive_classify(KParams kp, const char* __restrict__ bsrc,
+                                                              size_t bpitch, float thr,
+                                                              unsigned* __restrict__ list,
+                                                              unsigned* __restrict__ count) {
+    const PixelCoord pc = pixel_of(kp);
+    bool refine = false;
+    if (pc.active) {
+        auto px = [&](int r, int x) {
+            return reinterpret_cast<const float4*>(bsrc + static_cast<size_t>(r) * bpitch)[x];
+        };
+        const float4 p = px(pc.r, pc.x);
+        refine = ad_refines(AdRows{kp.height, kp.y0, kp.stripe, kp.period, kp.out_rows}, kp.width, pc.r, pc.x, pc.y,
+                            thr, p, px);
+        if (!refine) store_px(kp, pc.r, pc.x, p);
+    }
+    const unsigned long long m = __ballot(refine);
+    if (m) {  // wave-uniform
+        const unsigned pos = ad_append(count, m);
+        if (refine)
+            list[pos] = static_cast<unsigned>(pc.r) * static_cast<unsigned>(kp.width) + static_cast<unsigned>(pc.x);
+    }
+}
+
+// kp: the SAMPLE frame (fill_kparams with ss = n), dst / pitch / rgb the output's. One wave
+// per possible chunk of 64 / n^2 listed pixels (waves past the list's end exit at once, as
+// k_accel_tail's): lane l holds sample (l & (n-1), (l >> log2 n) & (n-1)) of the chunk's
+// pixel l >> 2 log2 n. Every bounce walks per lane -- a wave's rays come from several
+// pixels -- and a ray's value does not depend on the walk's form, so each sample has the
+// bits the supersampling k_accel instance gives it; the filter is that instance's xor
+// butterfly over this layout, x rounds then y rounds, then the exact 1 / n^2.
+// (With the frame's own walk policy instead -- packets for camera rays and their shadows --
+// the passes behind B cost the same: car 1080p n = 2, threshold 1/16, 0.418 ms against
+// 0.413 all per lane; DESIGN.md "Adaptive supersampling".)
+template <bool MT, bool DISP>
+__global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel_refine(AccelPtrs A, const float4* __restrict__ mat,
+                                                                        KParams kp,
+                                                                        const unsigned* __restrict__ list,
+                                                                        const unsigned* __restrict__ count) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    unsigned short* stt =
+        reinterpret_cast<unsigned short*>(lds_stack + static_cast<size_t>(kp.lane_stack) * blockDim.x) + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int sh = 31 - __builtin_clz(kp.ss);  // log2 n
+    const unsigned total = *count;
+    const unsigned long long chunk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const unsigned long long k = (chunk << (6 - 2 * sh)) + static_cast<unsigned>(lane >> (2 * sh));
+    if ((chunk << (6 - 2 * sh)) >= total) return;  // wave-uniform
+    const unsigned ow = static_cast<unsigned>(kp.width >> sh);  // the output's width
+    bool alive = k < total;
+    int r = 0, x = 0;  // the output pixel
+    Ray ray{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 1.f)};
+    // the sample's image row: image_row of the sample frame at n * r is n times the output's
+    auto sample_y = [&]() { return image_row(kp, r << sh) + ((lane >> sh) & (kp.ss - 1)); };
+    if (alive) {
+        const unsigned px = list[k];
+        r = static_cast<int>(px / ow);
+        x = static_cast<int>(px - static_cast<unsigned>(r) * ow);
+        ray = primary_ray(kp, (x << sh) + (lane & (kp.ss - 1)), sample_y());
+    }
+    const bool have = alive;
+    V acc = mk(0.f, 0.f, 0.f), att = mk(1.f, 1.f, 1.f);
+    WalkCount wc{0u, 0u, 0u, 0u};
+    for (int depth = 0; depth < kp.maxBounces; ++depth) {
+        if (__ballot(alive) == 0) break;
+        bounce_step<false, false, MT, !MT>(A, mat, kp, depth, ray, alive, acc, att, sample_y, stk, stt,
+                                           kp.lane_stack, wc, nullptr, 0, 0);
+    }
+    // lanes past the list's end hold zeros; a pixel's n^2 lanes are all in or all out
+    for (int b = 1; b < kp.ss * kp.ss; b <<= 1)
+        acc = acc + mk(__shfl_xor(acc.x, b), __shfl_xor(acc.y, b), __shfl_xor(acc.z, b));
+    const float w = 1.0f / static_cast<float>(kp.ss * kp.ss);  // a power of two: exact
+    if (have && (lane & (kp.ss * kp.ss - 1)) == 0) {
+        KParams ko = kp;  // the output frame's row mapping, for RT_FORMAT_RGBA32F_IMAGE
+        ko.y0 = kp.y0 >> sh;
+        ko.stripe = kp.stripe >> sh;
+        ko.period = kp.period >> sh;
+        store_px<DISP ? kStoreDisplay : kStoreFloat>(ko, r, x, make_float4(acc.x * w, acc.y * w, acc.z * w, 1.0f));
+    }
+}
+
+// The general path's filter: k_box_filter with the rule applied to the corner samples
+// (B(p) is sample (0, 0) of p's block: 2 (n x) / (n resX) and (n y) / (n resY) are the
+// float32 values 2 x / resX and y / resY). *count: the refined pixels (rt_adaptive_stats).
+template <int N, bool DISP = false>
+__global__ __launch_bounds__(256) void k_box_filter_adaptive(const char* __restrict__ src, size_t src_pitch,
+                                                             char* __restrict__ dst, size_t pitch, int width,
+                                                             int height, int y0, int stripe, int period,
+                                                             int out_rows, int format, float thr,
+                                                             unsigned* __restrict__ count) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int r = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const AdRows m{height, y0, stripe, period, out_rows};
+    const int y = r < out_rows ? ad_image_row(m, r) : 0;
+    const bool active = x < width && r < out_rows && y < height;
+    bool refine = false;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (active) {
+        auto px = [&](int rr, int xx) {
+            return *reinterpret_cast<const float4*>(src + static_cast<size_t>(rr) * N * src_pitch +
+                                                    static_cast<size_t>(xx) * N * sizeof(float4));
+        };
+        v = px(r, x);
+        refine = ad_refines(m, width, r, x, y, thr, v, px);
+        if (refine) {
+            v = box_y<N, N>(src + static_cast<size_t>(r) * N * src_pitch + static_cast<size_t>(x) * N * sizeof(float4),
+                            src_pitch);
+            const float w = 1.0f / static_cast<float>(N * N);
+            v = make_float4(v.x * w, v.y * w, v.z * w, v.w * w);
+        }
+    }
+    const unsigned long long rm = __ballot(refine);
+    if (rm) ad_append(count, rm);
+    if (!active) return;
+    if (DISP) {
+        store_display(dst + static_cast<size_t>(r) * pitch + static_cast<size_t>(x) * display_bytes(format), format, v);
+        return;
+    }
+    if (format == RT_FORMAT_RGB32F) {
+        float* p = reinterpret_cast<float*>(dst + static_cast<size_t>(r) * pitch) + 3 * x;
+        p[0] = v.x;
+        p[1] = v.y;
+        p[2] = v.z;
+        return;
+    }
+    const int row = format == RT_FORMAT_RGBA32F_IMAGE ? y : r;
+    reinterpret_cast<float4*>(dst + static_cast<size_t>(row) * pitch)[x] = v;
+}
+
 __global__ void k_pack_prims(const float4* __restrict__ geo_lin, const int* __restrict__ prim_shape,
                              const int* __restrict__ prim_seq, int P, float4* __restrict__ prims) {
     int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3030,6 +3220,20 @@ struct rt_ctx {
     bool convert_pass = false;  // rt_debug_convert_pass
     char* ss_buf = nullptr;
     size_t ss_bytes = 0;
+    // rt_set_adaptive: with samples > 1 and adaptive >= 0 a dispatch refines only the pixels
+    // whose one-sample value contrasts with a neighbour's. Frames k_accel renders: the
+    // one-sample frame B into ss_buf (sized for the output frame), k_adaptive_classify,
+    // k_accel_refine over ad_list; every other frame: the sample frame into ss_buf and
+    // k_box_filter_adaptive. ad_count: the refined pixels, zeroed in stream order by each
+    // adaptive dispatch; ad_from: the context (this one, brute or mtc) whose ad_count and
+    // ad_pixels are the last adaptive dispatch's (rt_adaptive_stats).
+    float adaptive = -1.0f;
+    unsigned* ad_list = nullptr;
+    size_t ad_cap = 0;
+    unsigned* ad_count = nullptr;
+    unsigned long long ad_pixels = 0;
+    bool ad_ran = false;  // the last launch() ran adaptively
+    rt_ctx* ad_from = nullptr;
     unsigned long long* stats_dev = nullptr;
     int cu_count = 256;
     int lane_from_depth = -1;  // bounces >= this use the per-lane walk (0: all, large: none;
@@ -4506,6 +4710,7 @@ void inherit(rt_ctx* b, const rt_ctx* c) {
     b->scene_stack = c->scene_stack;
     b->lane_stack_override = c->lane_stack_override;
     b->ss_general = c->ss_general;
+    b->adaptive = c->adaptive;
     b->convert_pass = c->convert_pass;
 }
 
@@ -4628,6 +4833,7 @@ int render_frame(rt_ctx* c, const KParams& kp, rt_ctx** from) {
     t->timing = false;  // the sub-context's own events would not be read: this context's time it
     if (!c->timing) {
         const int rc = launch(t, kt, false);
+        if (t->ad_ran) c->ad_from = t;
         c->last_kind = t->last_kind;
         c->timed = false;  // no events recorded for this dispatch
         return rc;
@@ -4640,6 +4846,7 @@ int render_frame(rt_ctx* c, const KParams& kp, rt_ctx** from) {
     HIP_TRY(hipEventRecord(e0, c->stream));
     const int rc = launch(t, kt, false);
     if (rc != RT_OK) return rc;
+    if (t->ad_ran) c->ad_from = t;
     HIP_TRY(hipEventRecord(e1, c->stream));
     c->last0 = e0;
     c->last1 = e1;
@@ -4654,6 +4861,16 @@ int render_frame(rt_ctx* c, const KParams& kp, rt_ctx** from) {
 // (`out`: the dispatch's own KParams, `out.ss` = n; rt_ctx::samples).
 void launch_box_filter(rt_ctx* c, const KParams& out) {
     const int n = out.ss, w = out.width / n, rows = out.out_rows / n;
+    if (n > 1 && c->adaptive >= 0.0f) {  // rt_set_adaptive's general path (launch() zeroed ad_count)
+        const bool disp = out.rgb >= RT_FORMAT_RGBA8;
+        auto afn = n == 2   ? (disp ? k_box_filter_adaptive<2, true> : k_box_filter_adaptive<2>)
+                   : n == 4 ? (disp ? k_box_filter_adaptive<4, true> : k_box_filter_adaptive<4>)
+                            : (disp ? k_box_filter_adaptive<8, true> : k_box_filter_adaptive<8>);
+        hipLaunchKernelGGL(afn, dim3((w + 63) / 64, (rows + 3) / 4), dim3(256), 0, c->stream, c->ss_buf,
+                           static_cast<size_t>(out.width) * sizeof(float4), out.dst, out.pitch, w, out.height / n,
+                           out.y0 / n, out.stripe / n, out.period / n, rows, out.rgb, c->adaptive, c->ad_count);
+        return;
+    }
     auto kfn = n == 2 ? k_box_filter<2> : n == 4 ? k_box_filter<4> : k_box_filter<8>;
     if (out.rgb >= RT_FORMAT_RGBA8)  // n == 1: the conversion alone (rt_debug_convert_pass)
         kfn = n == 1   ? k_box_filter<1, true>
@@ -4665,8 +4882,39 @@ void launch_box_filter(rt_ctx* c, const KParams& out) {
                        out.y0 / n, out.stripe / n, out.period / n, rows, out.rgb);
 }
 
+// The pixels a dispatch of the OUTPUT frame `k` writes: its compact rows below the frame's end.
+unsigned long long dispatch_pixels(const KParams& k) {
+    if (k.period == k.stripe)  // contiguous rows from y0
+        return static_cast<unsigned long long>(std::max(0, std::min(k.out_rows, k.height - k.y0))) * k.width;
+    unsigned long long rows = 0;
+    for (long long s = 0; s * k.stripe < k.out_rows; ++s) {
+        const long long base = k.y0 + s * k.period;
+        if (base >= k.height) break;
+        rows += std::min<long long>({k.stripe, k.out_rows - s * k.stripe, k.height - base});
+    }
+    return rows * static_cast<unsigned long long>(k.width);
+}
+
+// Passes 2 and 3 of rt_set_adaptive's fast path, behind the one-sample render of B into
+// c->ss_buf: `out` is B's frame with the dispatch's dst / pitch / format, `smp` the sample
+// frame. The host never reads the list's length: the refine grid is the worst case.
+void launch_adaptive(rt_ctx* c, const AccelPtrs& A, const KParams& out, const KParams& smp) {
+    const dim3 grid((out.width + kTileW - 1) / kTileW, (out.out_rows + kTileH - 1) / kTileH);
+    hipLaunchKernelGGL(k_adaptive_classify, grid, dim3(kBlock), 0, c->stream, out, c->ss_buf,
+                       static_cast<size_t>(out.width) * sizeof(float4), c->adaptive, c->ad_list, c->ad_count);
+    const bool disp = smp.rgb >= RT_FORMAT_RGBA8;
+    auto kfn = c->accel.mt ? (disp ? k_accel_refine<true, true> : k_accel_refine<true, false>)
+                           : (disp ? k_accel_refine<false, true> : k_accel_refine<false, false>);
+    const unsigned long long per = 64 / (smp.ss * smp.ss);  // pixels per wave
+    const unsigned long long px = static_cast<unsigned long long>(out.width) * out.out_rows;
+    const size_t lds = static_cast<size_t>(smp.lane_stack) * 64 * 6;
+    hipLaunchKernelGGL(kfn, dim3(static_cast<unsigned>((px + per - 1) / per)), dim3(64), lds, c->stream, A, c->mat,
+                       smp, c->ad_list, c->ad_count);
+}
+
 int launch(rt_ctx* c, const KParams& kin, bool stats) {
     c->frame_ev_set = false;
+    c->ad_ran = false;
     if (const int rc = flush_updates(c)) return rc;  // rt_update_shapes / rt_update_nodes since the last dispatch
     if (kin.out_rows == 0) return RT_OK;
     dim3 grid((kin.width + kTileW - 1) / kTileW, (kin.out_rows + kTileH - 1) / kTileH);
@@ -4680,14 +4928,46 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
     // no SS form), rt_debug_ss_general -- is the one-sample render of the sample frame into
     // the context's scratch surface, then k_box_filter (general).
     const bool ss = !stats && kin.ss > 1;
-    const bool ss_fused = ss && kind == RT_KERNEL_ACCEL && !c->tile_times && !c->ss_general;
+    const bool ss_accel = ss && kind == RT_KERNEL_ACCEL && !c->tile_times && !c->ss_general;
+    // rt_set_adaptive: where k_accel would reduce the samples (fast path), it renders the
+    // one-sample frame B into the scratch surface instead -- this dispatch from here on, with
+    // every setting of a one-sample frame -- and launch_adaptive refines the contrast pixels;
+    // every other frame keeps the general path with the adaptive filter kernel.
+    const bool adaptive = ss && c->adaptive >= 0.0f;
+    const bool ad_fast = adaptive && ss_accel;
+    const bool ss_fused = ss_accel && !ad_fast;
     // rt_debug_convert_pass: a one-sample display frame the same way, float frame first, then
     // the filter kernel's conversion (the measurement's baseline, tools/bench_formats.py)
-    const bool filter = ss ? !ss_fused : !stats && c->convert_pass && kin.rgb >= RT_FORMAT_RGBA8;
-    KParams kp = kin;
-    if (filter) {
-        const size_t spitch = static_cast<size_t>(kin.width) * sizeof(float4);
-        const size_t need = spitch * static_cast<size_t>(kin.out_rows);
+    const bool filter = ss ? !ss_accel : !stats && c->convert_pass && kin.rgb >= RT_FORMAT_RGBA8;
+    KParams kout = kin;  // adaptive: the one-sample output frame, B's, with the dispatch's dst / pitch / format
+    if (adaptive) {      // (the dispatch scaled it by n: every value is a multiple, the floats exact)
+        const int n = kin.ss;
+        kout.width = kin.width / n;
+        kout.height = kin.height / n;
+        kout.y0 = kin.y0 / n;
+        kout.stripe = kin.stripe / n;
+        kout.period = kin.period / n;
+        kout.out_rows = kin.out_rows / n;
+        kout.resX = kin.resX / static_cast<float>(n);
+        kout.resY = kin.resY / static_cast<float>(n);
+        kout.ss = 1;
+    }
+    KParams kp = ad_fast ? kout : kin;
+    if (adaptive) {
+        if (!c->ad_count && hipMalloc(&c->ad_count, 4 * sizeof(unsigned)) != hipSuccess) return RT_ERR_NO_MEMORY;
+        const size_t cap = static_cast<size_t>(kout.width) * static_cast<size_t>(kout.out_rows);
+        if (ad_fast && cap > c->ad_cap) {
+            HIP_TRY(sync_stream(c));
+            hipFree(c->ad_list);
+            c->ad_list = nullptr;
+            c->ad_cap = 0;
+            if (hipMalloc(&c->ad_list, cap * sizeof(unsigned)) != hipSuccess) return RT_ERR_NO_MEMORY;
+            c->ad_cap = cap;
+        }
+    }
+    if (filter || ad_fast) {
+        const size_t spitch = static_cast<size_t>(kp.width) * sizeof(float4);
+        const size_t need = spitch * static_cast<size_t>(kp.out_rows);
         if (need != c->ss_bytes) {
             HIP_TRY(sync_stream(c));
             hipFree(c->ss_buf);
@@ -4709,6 +4989,13 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
         e1 = c->ring1[c->ring_used];
     }
     if (rec) HIP_TRY(hipEventRecord(e0, c->stream));
+    if (adaptive) {
+        // the refined-pixel counter, zeroed in stream order; its last value stays for rt_adaptive_stats
+        HIP_TRY(hipMemsetAsync(c->ad_count, 0, sizeof(unsigned), c->stream));
+        c->ad_ran = true;
+        c->ad_from = c;
+        c->ad_pixels = dispatch_pixels(kout);
+    }
     bool order_after = false;  // e1 already recorded between the render and the order kernel
     if (stats) {
         hipLaunchKernelGGL(k_lane<true>, grid, dim3(kBlock), lds, c->stream, c->geo_leaf, c->geo_lin, c->mat,
@@ -5012,6 +5299,11 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
             c->tail_parity = 1 - c->tail_parity;
         }
         if (filter) launch_box_filter(c, kin);
+        if (ad_fast) {
+            KParams smp = kin;  // the sample frame, walked per lane
+            smp.lane_stack = k2.lane_stack;
+            launch_adaptive(c, A, kout, smp);
+        }
         if (k2.tile_cost) {
             // the next frame's order; stream-ordered after this dispatch (and after its
             // end event, so rt_kernel_times is the render kernel alone), before the next
@@ -5300,6 +5592,8 @@ int rt_destroy(rt_ctx* c) {
     hipFree(c->staging_idx);
     hipFree(c->img);
     hipFree(c->ss_buf);
+    hipFree(c->ad_list);
+    hipFree(c->ad_count);
     hipFree(c->stats_dev);
     hipFree(c->trace_in);
     hipFree(c->trace_hits);
@@ -5703,6 +5997,23 @@ int rt_dispatch_rows_ex(rt_ctx* c, int width, int height, int y0, int stripe, in
 int rt_set_samples(rt_ctx* c, int n) {
     if (!c || (n != 1 && n != 2 && n != 4 && n != 8)) return RT_ERR_INVALID;
     c->samples = n;
+    return RT_OK;
+}
+
+int rt_set_adaptive(rt_ctx* c, float threshold) {
+    if (!c || threshold != threshold) return RT_ERR_INVALID;  // NaN: the setting stays
+    c->adaptive = threshold < 0.0f ? -1.0f : threshold;
+    return RT_OK;
+}
+
+int rt_adaptive_stats(rt_ctx* c, uint64_t* refined, uint64_t* pixels) {
+    if (!c || !c->ad_from) return RT_ERR_INVALID;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    HIP_TRY(sync_stream(c));  // the sub-contexts (brute, mtc) render on this stream
+    unsigned n = 0;
+    HIP_TRY(hipMemcpy(&n, c->ad_from->ad_count, sizeof n, hipMemcpyDeviceToHost));
+    if (refined) *refined = n;
+    if (pixels) *pixels = c->ad_from->ad_pixels;
     return RT_OK;
 }
 

@@ -239,6 +239,8 @@ RT_SYMBOLS = {
     "rt_set_kernel_timing": (_I, [_P, _I]),
     "rt_set_tail": (_I, [_P, _I]),
     "rt_set_samples": (_I, [_P, _I]),
+    "rt_set_adaptive": (_I, [_P, C.c_float]),
+    "rt_adaptive_stats": (_I, [_P, _P, _P]),
     "rt_trace_rays": (_I, [_P, _P, _I, _P, _I]),
     "rt_trace_rays_host": (_I, [_P, _P, _I, _P, _I]),
     "rt_trace_pixels": (_I, [_P, _I, _I, _P, _I, _P]),
@@ -784,6 +786,18 @@ class ComputeShader:
         """rt_set_samples: every pixel is the mean of n x n samples (n in 1, 2, 4, 8) on the regular
         sub-pixel grid, i.e. the box filter of the n*W x n*H frame; applies to every dispatch form."""
         self._chk(self._lib.rt_set_samples(self._h, int(n)), "rt_set_samples")
+
+    def set_adaptive(self, threshold):
+        """rt_set_adaptive: with set_samples(n > 1), only the pixels whose one-sample value differs
+        from a 4-neighbour's by more than `threshold` in some channel take the n x n samples; the
+        rest keep the one-sample value. threshold < 0: off (default); inf: the one-sample frame."""
+        self._chk(self._lib.rt_set_adaptive(self._h, C.c_float(threshold)), "rt_set_adaptive")
+
+    def adaptive_stats(self):
+        """(refined, pixels) of the last dispatch that ran adaptively (rt_adaptive_stats; waits for it)."""
+        refined, pixels = C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.rt_adaptive_stats(self._h, C.byref(refined), C.byref(pixels)), "rt_adaptive_stats")
+        return refined.value, pixels.value
 
     @staticmethod
     def make_rays(origins, dirs, limits=None):
