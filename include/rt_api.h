@@ -496,6 +496,77 @@ int rt_trace_rays_host(struct rt_ctx* ctx, const rt_ray* rays, int n, rt_hit* hi
  * outside the frame. */
 int rt_trace_pixels(struct rt_ctx* ctx, int width, int height, const int* xy, int n, rt_hit* hits);
 
+/* Geometry buffer: per pixel, the shape under it, its depth, the surface normal and the hit
+ * point -- what a host needs to composite raster content over the traced image, to outline
+ * or mask shapes, or for screen-space effects. One kernel of its own walks the camera rays
+ * of whole 8x8 tiles as wave64 packets; no ray or hit list crosses the bus.
+ *
+ * Planes. Each plane is a caller surface with its own pitch in bytes; a NULL pointer means
+ * the plane is not wanted (at least one must be given).
+ *
+ * Rows. The compact rows of rt_dispatch_rows_ex: row r in [0, out_rows) of every plane is
+ * image row y(r) = y0 + (r / stripe) * period + r % stripe. A row with y(r) >= height is left
+ * untouched in every plane. Within a row only the first `width` pixels are written (4*width
+ * or 16*width bytes); not one byte after them is touched.
+ *
+ * What a pixel holds. For pixel (x, y), take the camera ray a dispatch generates (current
+ * camera, rt_params::resX / resY, NDC 2x/resX - 1, 1 - 2y/resY) and the answer
+ * rt_trace_pixels gives for it: the closest INNER hit of the reference's BVH branch over the
+ * context's current tree and shapes, ties to the first shape in the reference's walk order.
+ *   shape     int32 index into the uploaded FlatShape array; -1 on a miss.
+ *   depth     float32 rt_hit::distance, the shader's distance(origin, hit); 1e20f on a miss.
+ *   position  (p.x, p.y, p.z, 1.0f) with p = origin + t * dir, the hit point the shader
+ *             shades (the point get_intersection returns); (0, 0, 0, 0) on a miss, so w is
+ *             a hit mask.
+ *   normal    (n.x, n.y, n.z, 0.0f) with n = getNormalFromShape at p: for a sphere
+ *             n = v * (1.0f / sqrtf((v.x*v.x + v.y*v.y) + v.z*v.z)) with v = p - centre, all
+ *             in float32; for a plane, wall or triangle the record's planeNormal, its bits
+ *             unchanged; (0, 0, 0, 0) on a miss. The normal is not flipped towards the
+ *             viewer: it is the value the shading uses.
+ * Every value is exact: the same bits from every kernel variant.
+ *
+ * What applies: useMollerTrumbore, rt_set_kernel and rt_set_tree, exactly as they do to
+ * rt_trace_pixels. What does not enter: useBVH, light, bounces, Fresnel, rt_set_samples,
+ * rt_set_adaptive, latency mode, schedule and tail. With rt_set_samples(n) the buffer
+ * describes sample (0, 0) of each pixel: the frame B of rt_set_adaptive.
+ *
+ * Like a query, the call first applies pending rt_update_shapes / rt_update_nodes /
+ * rt_animate work as one refit. It leaves alone the surface, rt_accel_info::last_kernel, the
+ * record of rt_kernel_times / rt_last_kernel_ms, rt_sync_frame's marker, the tile cost order
+ * and rt_adaptive_stats.
+ *
+ * Errors, returned before anything is launched. RT_ERR_INVALID: out == NULL; all four
+ * planes NULL; width, height or stripe <= 0, y0 or out_rows < 0, period < stripe (as
+ * rt_dispatch_rows_ex); a shape or depth pitch below 4*width or not 4-byte aligned; a normal
+ * or position pitch below 16*width or not 16-byte aligned; a misaligned plane pointer (4
+ * bytes for shape and depth, 16 for normal and position); a limit of the one-sample dispatch
+ * broken (more than 65,535 rows of 8x8 tiles, width * out_rows >= 2^32). RT_ERR_NO_SCENE
+ * without a scene, camera or params, as for rt_trace_pixels. out_rows == 0 is RT_OK and
+ * launches nothing. A scene without nodes makes every pixel a miss.
+ *
+ * Group frames (rt_group.h) have no geometry buffer. A view-space depth is
+ * dot(position - camera.Position, camera.Front); there is no plane for it. */
+typedef struct rt_gbuffer {          /* planes; a NULL pointer = plane not wanted */
+    int*   shape;    size_t shape_pitch;     /*  4 B / pixel */
+    float* depth;    size_t depth_pitch;     /*  4 B / pixel */
+    float* normal;   size_t normal_pitch;    /* 16 B / pixel */
+    float* position; size_t position_pitch;  /* 16 B / pixel */
+} rt_gbuffer;
+
+RT_STATIC_ASSERT(sizeof(rt_gbuffer) == 8 * sizeof(void*) && offsetof(rt_gbuffer, shape_pitch) == sizeof(void*) &&
+                 offsetof(rt_gbuffer, depth) == 2 * sizeof(void*) && offsetof(rt_gbuffer, normal) == 4 * sizeof(void*) &&
+                 offsetof(rt_gbuffer, position) == 6 * sizeof(void*) &&
+                 offsetof(rt_gbuffer, position_pitch) == 7 * sizeof(void*), "rt_gbuffer");
+
+/* Device pointers; stream-ordered on the context's stream, asynchronous. */
+int rt_dispatch_gbuffer(struct rt_ctx* ctx, int width, int height, int y0, int stripe, int period,
+                        int out_rows, const rt_gbuffer* out);
+
+/* Host pointers, the whole frame (rows [0, height)), staged through buffers the context keeps
+ * between calls; returns when the planes are in host memory. Pointers and pitches are checked
+ * as above. */
+int rt_gbuffer_host(struct rt_ctx* ctx, int width, int height, const rt_gbuffer* host_out);
+
 /* Accelerator statistics for the uploaded scene. */
 int rt_accel_info_get(struct rt_ctx* ctx, rt_accel_info* out);
 

@@ -39,6 +39,10 @@
 //       the caller's rays, or the camera rays of the caller's pixels, one per lane
 //       through lane_walk over the accelerator (k_trace) or through k_lane's literal
 //       walk (k_trace_ref); closest hit or occlusion within a limit per ray.
+//   k_gbuffer<MT, LANE> / k_gbuffer_ref : geometry buffers (rt_dispatch_gbuffer): the closest
+//       hit of every pixel's camera ray as planes of shape, depth, normal and position. One
+//       8x8 tile per wave through packet_walk (or lane_walk for a camera beyond the
+//       accelerator's origin bound); k_gbuffer_ref is k_lane's literal walk.
 //   k_tile_order / k_cost_dilate : the next frame's dispatch order from the tile
 //       costs a k_accel dispatch recorded (rt_set_schedule).
 //   k_refit / k_inf_slots : boxes and cones of moved shapes (rt_animate,
@@ -2128,6 +2132,96 @@ __global__ __launch_bounds__(kBlock) void k_trace_ref(TraceArgs q, KParams kp) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Geometry buffers (rt_dispatch_gbuffer / rt_gbuffer_host): the closest hit of every pixel's
+// camera ray as up to four planes (include/rt_api.h: shape, depth, normal, position).
+
+// One pixel of every plane the caller gave (a wave-uniform choice), compact row r, column x.
+// Streaming stores, one per plane: the kernels never read the planes back.
+typedef float rt_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_gbuffer(const rt_gbuffer& g, int r, int x, int shape, float depth, V n, V p,
+                                              float w) {
+    const size_t row = static_cast<size_t>(r);
+    if (g.shape)
+        __builtin_nontemporal_store(shape,
+                                    reinterpret_cast<int*>(reinterpret_cast<char*>(g.shape) + row * g.shape_pitch) + x);
+    if (g.depth)
+        __builtin_nontemporal_store(
+            depth, reinterpret_cast<float*>(reinterpret_cast<char*>(g.depth) + row * g.depth_pitch) + x);
+    if (g.normal)
+        __builtin_nontemporal_store(
+            rt_f32x4{n.x, n.y, n.z, 0.0f},
+            reinterpret_cast<rt_f32x4*>(reinterpret_cast<char*>(g.normal) + row * g.normal_pitch) + x);
+    if (g.position)
+        __builtin_nontemporal_store(
+            rt_f32x4{p.x, p.y, p.z, w},
+            reinterpret_cast<rt_f32x4*>(reinterpret_cast<char*>(g.position) + row * g.position_pitch) + x);
+}
+
+// One 8x8 tile per wave in row-major tile order (tile_pixel), any number of waves to a block,
+// over the accelerator: the tile's camera rays as one packet (packet_walk: the stack in VGPRs,
+// no LDS), or, LANE, one ray per lane with k_trace's LDS stacks -- the frames whose camera lies
+// beyond the accelerator's origin bound, and the A/B of tools/bench_gbuffer.py. Rays that miss
+// the root's box (accel_tile's test, from the kernel arguments) skip the walk: the sky tiles.
+// No shading state is carried, so k_accel's register cap does not apply.
+template <bool MT, bool LANE>
+__global__ __launch_bounds__(kBlock) void k_gbuffer(AccelPtrs A, rt_gbuffer g, KParams kp) {
+    extern __shared__ int lds_stack[];
+    const int tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (tile >= kp.tiles) return;  // wave-uniform
+    const PixelCoord pc = tile_pixel(kp, tile);
+    const Ray ray = primary_ray(kp, pc.x, pc.y);
+    bool alive = pc.active;
+    if (kp.root_ok) {
+        V rlo = mk(kp.root_lo[0], kp.root_lo[1], kp.root_lo[2]), rhi = mk(kp.root_hi[0], kp.root_hi[1], kp.root_hi[2]);
+        if (kp.root_ok == 2) {
+            const float4 a = A.anodes[4 * static_cast<size_t>(A.N - 1)], b = A.anodes[4 * static_cast<size_t>(A.N - 1) + 1];
+            rlo = mk(a.x, a.y, a.z);
+            rhi = mk(b.x, b.y, b.z);
+        }
+        alive = alive && ray_aabb(ray.o, inv_dir(ray.d), rlo, rhi);
+    }
+    Best best{1e20f, 0x7fffffff, 0.f, -1};
+    bool unused = false;
+    WalkCount wc{0u, 0u, 0u, 0u};
+    if (LANE) {
+        int* stk = lds_stack + threadIdx.x;
+        unsigned short* stt =
+            reinterpret_cast<unsigned short*>(lds_stack + static_cast<size_t>(kp.lane_stack) * blockDim.x) +
+            threadIdx.x;
+        lane_walk<false, false, false, MT, true>(A, ray, alive, 0.f, best, unused, stk, stt, blockDim.x,
+                                                 kp.lane_stack, wc);
+    } else {
+        packet_walk<false, false, false, MT>(A, ray, alive, 0.f, best, unused, wc);
+    }
+    if (!pc.active) return;
+    if (best.slot < 0) {
+        store_gbuffer(g, pc.r, pc.x, -1, 1e20f, mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f), 0.0f);
+        return;
+    }
+    const V p = hit_point(ray, best.t);
+    store_gbuffer(g, pc.r, pc.x, A.prim_shape[best.slot], best.d, shape_normal(load_prim(A.prims, best.slot), p), p,
+                  1.0f);
+}
+
+// The same planes from k_lane's literal walk over the reference tree alone (contexts without
+// a usable accelerator, RT_KERNEL_LANE / RT_KERNEL_PACKET): k_lane's blocks, pixels and stacks.
+__global__ __launch_bounds__(kBlock) void k_gbuffer_ref(rt_gbuffer g, KParams kp) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    const PixelCoord pc = pixel_of(kp);
+    if (!pc.active) return;
+    const Ray r = primary_ray(kp, pc.x, pc.y);
+    Counters c;
+    const LaneHit h = lane_closest_bvh<false>(kp, kp.nodes, kp.geo_leaf, r, stk, c);
+    if (!h.found) {
+        store_gbuffer(g, pc.r, pc.x, -1, 1e20f, mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f), 0.0f);
+        return;
+    }
+    const GeoRec rec = load_rec(kp.geo_leaf, h.slot);
+    store_gbuffer(g, pc.r, pc.x, rec.idx, h.d, shape_normal(rec, h.p), h.p, 1.0f);
+}
+
 // The general path of rt_set_samples: the sample frame was rendered by any kernel into a
 // scratch surface (compact rows, RGBA32F); one thread per output pixel applies the box
 // filter in the order rt_api.h fixes -- log2 N pairwise rounds along x, then along y,
@@ -3203,6 +3297,11 @@ struct rt_ctx {
     size_t trace_in_cap = 0;
     float4* trace_hits = nullptr;
     size_t trace_hits_cap = 0;
+    // rt_gbuffer_host: staging for the four planes, grown on demand and kept between calls
+    float4* gbuf_stage = nullptr;
+    size_t gbuf_stage_cap = 0;
+    int gbuf_walk = 0;    // rt_debug_gbuffer: 1 = the accelerated form walks per lane (diagnostics)
+    int gbuf_waves = 0;   // rt_debug_gbuffer: waves (tiles) per block, 0 = the default
     int kernel = RT_KERNEL_AUTO;
     int last_kind = 0;
     // own surface
@@ -5366,7 +5465,10 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
 // would walk (the context's own, or mtc's for Moller-Trumbore), or k_trace_ref's literal
 // walk when there is none or rt_set_kernel chose the lane / packet kernel. None of the
 // render state (last_kind, the timing ring, the frame marker, the cost order) is touched.
-int trace_launch(rt_ctx* c, const float4* rays, const int2* xy, int n, float4* hits, int mode) {
+// The context whose device scene a query or a geometry buffer reads, after its pending
+// scene writes went in as one refit: the context's own, or mtc for Moller-Trumbore.
+// *accel: its accelerator serves the walk (else the literal reference walk).
+int query_target(rt_ctx* c, rt_ctx** target, bool* accel) {
     if (const int rc = flush_updates(c)) return rc;
     const bool mt = c->params.useMollerTrumbore != 0;
     rt_ctx* t = c;
@@ -5379,8 +5481,16 @@ int trace_launch(rt_ctx* c, const float4* rays, const int2* xy, int n, float4* h
             if (b->accel_ok) t = b;
         }
     }
-    const bool accel = (c->kernel == RT_KERNEL_AUTO || c->kernel == RT_KERNEL_ACCEL) && t->accel_ok &&
-                       t->accel.mt == mt;
+    *target = t;
+    *accel = (c->kernel == RT_KERNEL_AUTO || c->kernel == RT_KERNEL_ACCEL) && t->accel_ok && t->accel.mt == mt;
+    return RT_OK;
+}
+
+int trace_launch(rt_ctx* c, const float4* rays, const int2* xy, int n, float4* hits, int mode) {
+    rt_ctx* t = c;
+    bool accel = false;
+    if (const int rc = query_target(c, &t, &accel)) return rc;
+    const bool mt = c->params.useMollerTrumbore != 0;
     KParams kp;
     std::memset(&kp, 0, sizeof kp);
     kp.geo_leaf = t->geo_leaf;
@@ -5439,6 +5549,103 @@ int trace_staged(rt_ctx* c, const void* in, size_t in_bytes, bool pixels, int n,
     HIP_TRY(hipMemcpyAsync(hits, c->trace_hits, static_cast<size_t>(n) * sizeof(rt_hit), hipMemcpyDeviceToHost,
                            c->stream));
     HIP_TRY(sync_stream(c));
+    return RT_OK;
+}
+
+// Geometry buffers. The checks of rt_dispatch_gbuffer and rt_gbuffer_host (include/rt_api.h),
+// before anything is launched; RT_OK with *run = false when there is nothing to launch.
+// Tiles per block: one, as k_accel and k_trace. Two and four measured equal or slower
+// (tools/bench_gbuffer.py's a_w2 and a_w4, DESIGN.md §4 "Geometry buffers").
+constexpr int kGbufWaves = 1;
+
+int gbuffer_check(const rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows,
+                  const rt_gbuffer* out, bool* run) {
+    *run = false;
+    if (!c || !out || (!out->shape && !out->depth && !out->normal && !out->position)) return RT_ERR_INVALID;
+    if (!c->have_scene || !c->have_cam || !c->have_params) return RT_ERR_NO_SCENE;
+    if (width <= 0 || height <= 0 || stripe <= 0 || period < stripe || out_rows < 0 || y0 < 0) return RT_ERR_INVALID;
+    const struct {
+        const void* p;
+        size_t pitch, px;
+    } planes[4] = {{out->shape, out->shape_pitch, 4},
+                   {out->depth, out->depth_pitch, 4},
+                   {out->normal, out->normal_pitch, 16},
+                   {out->position, out->position_pitch, 16}};
+    for (const auto& pl : planes)
+        if (pl.p && (pl.pitch < static_cast<size_t>(width) * pl.px || pl.pitch % pl.px != 0 ||
+                     reinterpret_cast<uintptr_t>(pl.p) % pl.px != 0))
+            return RT_ERR_INVALID;
+    if ((static_cast<long long>(out_rows) + kTileH - 1) / kTileH > 65535 ||
+        static_cast<unsigned long long>(width) * static_cast<unsigned long long>(out_rows) >= (1ull << 32))
+        return RT_ERR_INVALID;
+    *run = out_rows > 0;
+    return RT_OK;
+}
+
+// One geometry-buffer launch on the context's stream: pending scene writes first, as one
+// refit (query_target); then k_gbuffer over the accelerator a query would walk -- as packets
+// while the camera lies inside its origin bound, per lane beyond it -- or k_gbuffer_ref's
+// literal walk. Like a query it touches none of the render state.
+int gbuffer_launch(rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows,
+                   const rt_gbuffer& g) {
+    rt_ctx* t = c;
+    bool accel = false;
+    if (const int rc = query_target(c, &t, &accel)) return rc;
+    const bool mt = c->params.useMollerTrumbore != 0;
+    KParams kp;
+    std::memset(&kp, 0, sizeof kp);
+    kp.geo_leaf = t->geo_leaf;
+    kp.geo_lin = t->geo_lin;
+    kp.nodes = t->nodes;
+    kp.S = t->S;
+    kp.N = t->N;
+    kp.I = t->I;
+    kp.max_stack = t->max_stack < 1 ? 1 : t->max_stack;
+    kp.useBVH = 1;
+    kp.useMT = mt ? 1 : 0;
+    kp.lane_stack = t->lane_stack_override > 0 ? t->lane_stack_override : t->accel.max_stack;
+    fill_camera(c->cam, kp);
+    kp.resX = c->params.resX;
+    kp.resY = c->params.resY;
+    kp.width = width;
+    kp.height = height;
+    kp.y0 = y0;
+    kp.stripe = stripe;
+    kp.period = period;
+    kp.out_rows = out_rows;
+    kp.tiles_x = (width + 7) / 8;
+    kp.tiles = kp.tiles_x * ((out_rows + 7) / 8);
+    if (!accel) {
+        const dim3 grid((width + kTileW - 1) / kTileW, (out_rows + kTileH - 1) / kTileH);
+        const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
+        hipLaunchKernelGGL(k_gbuffer_ref, grid, dim3(kBlock), lds, c->stream, g, kp);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    }
+    // the root's current bounds, as launch() passes them to k_accel
+    if (kp.N > 0 && t->nodes_on_device_newer) kp.root_ok = 2;
+    if (kp.N > 0 && !t->nodes_on_device_newer && static_cast<int>(t->host_nodes.size()) == kp.N) {
+        const FlatNode& rn = t->host_nodes[kp.N - 1];
+        kp.root_ok = 1;
+        kp.root_lo[0] = rn.boundsMin.x;
+        kp.root_lo[1] = rn.boundsMin.y;
+        kp.root_lo[2] = rn.boundsMin.z;
+        kp.root_hi[0] = rn.boundsMax.x;
+        kp.root_hi[1] = rn.boundsMax.y;
+        kp.root_hi[2] = rn.boundsMax.z;
+    }
+    // the packet form needs the shared origin inside the accelerator's bound (accel_usable)
+    const float cmag = std::max({std::fabs(kp.cam_pos.x), std::fabs(kp.cam_pos.y), std::fabs(kp.cam_pos.z)});
+    const bool lane = c->gbuf_walk == 1 || !(cmag <= t->accel.origin_lim);
+    int waves = c->gbuf_waves > 0 ? c->gbuf_waves : kGbufWaves;
+    // the lane form's stacks (lane_stack x 6 B a lane) within the 64 KB a block may ask for
+    while (lane && waves > 1 && static_cast<size_t>(kp.lane_stack) * 64 * waves * 6 > 65536) waves /= 2;
+    const dim3 grid((kp.tiles + waves - 1) / waves), block(64 * waves);
+    auto kfn = lane ? (mt ? k_gbuffer<true, true> : k_gbuffer<false, true>)
+                    : (mt ? k_gbuffer<true, false> : k_gbuffer<false, false>);
+    const size_t lds = lane ? static_cast<size_t>(kp.lane_stack) * block.x * 6 : 0;  // the packet form: no LDS
+    hipLaunchKernelGGL(kfn, grid, block, lds, c->stream, accel_ptrs(t), g, kp);
+    HIP_TRY(hipGetLastError());
     return RT_OK;
 }
 
@@ -5597,6 +5804,7 @@ int rt_destroy(rt_ctx* c) {
     hipFree(c->stats_dev);
     hipFree(c->trace_in);
     hipFree(c->trace_hits);
+    hipFree(c->gbuf_stage);
     hipFree(c->tail_queue);
     hipFree(c->tail_counts);
     hipFree(c->tile_times);
@@ -6223,6 +6431,51 @@ int rt_trace_pixels(rt_ctx* c, int width, int height, const int* xy, int n, rt_h
     return run ? trace_staged(c, xy, 2 * sizeof(int), true, n, hits, RT_TRACE_CLOSEST) : RT_OK;
 }
 
+int rt_dispatch_gbuffer(rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows,
+                        const rt_gbuffer* out) {
+    bool run;
+    if (const int rc = gbuffer_check(c, width, height, y0, stripe, period, out_rows, out, &run)) return rc;
+    if (!run) return RT_OK;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    return gbuffer_launch(c, width, height, y0, stripe, period, out_rows, *out);
+}
+
+int rt_gbuffer_host(rt_ctx* c, int width, int height, const rt_gbuffer* host_out) {
+    bool run;
+    if (const int rc = gbuffer_check(c, width, height, 0, 1, 1, height, host_out, &run)) return rc;
+    if (!run) return RT_OK;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    // the wanted planes side by side in the staging buffer, rows packed (every offset a multiple of 16 B)
+    const size_t px = static_cast<size_t>(width) * static_cast<size_t>(height);
+    const size_t small16 = (px * 4 + 15) / 16;
+    const size_t need = (host_out->shape ? small16 : 0) + (host_out->depth ? small16 : 0) +
+                        (host_out->normal ? px : 0) + (host_out->position ? px : 0);
+    if (const int rc = ensure_staging(c->gbuf_stage, c->gbuf_stage_cap, need)) return rc;
+    float4* at = c->gbuf_stage;
+    rt_gbuffer dev{};
+    const size_t w4 = static_cast<size_t>(width) * 4, w16 = static_cast<size_t>(width) * 16;
+    if (host_out->shape) dev.shape = reinterpret_cast<int*>(at), dev.shape_pitch = w4, at += small16;
+    if (host_out->depth) dev.depth = reinterpret_cast<float*>(at), dev.depth_pitch = w4, at += small16;
+    if (host_out->normal) dev.normal = reinterpret_cast<float*>(at), dev.normal_pitch = w16, at += px;
+    if (host_out->position) dev.position = reinterpret_cast<float*>(at), dev.position_pitch = w16, at += px;
+    if (const int rc = gbuffer_launch(c, width, height, 0, 1, 1, height, dev)) return rc;
+    const struct {
+        void* dst;
+        size_t dpitch;
+        const void* src;
+        size_t row;
+    } copies[4] = {{host_out->shape, host_out->shape_pitch, dev.shape, w4},
+                   {host_out->depth, host_out->depth_pitch, dev.depth, w4},
+                   {host_out->normal, host_out->normal_pitch, dev.normal, w16},
+                   {host_out->position, host_out->position_pitch, dev.position, w16}};
+    for (const auto& cp : copies)
+        if (cp.dst)
+            HIP_TRY(hipMemcpy2DAsync(cp.dst, cp.dpitch, cp.src, cp.row, cp.row, static_cast<size_t>(height),
+                                     hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(sync_stream(c));
+    return RT_OK;
+}
+
 }  // extern "C"
 
 extern "C" int rt_accel_info_get(rt_ctx* c, rt_accel_info* out) {
@@ -6460,6 +6713,16 @@ extern "C" int rt_debug_cost_dilate(rt_ctx* c, int r) {
 extern "C" int rt_debug_lane_stack(rt_ctx* c, int n) {
     if (!c || n < 0 || n > kMaxStack) return RT_ERR_INVALID;
     c->lane_stack_override = n;
+    return RT_OK;
+}
+
+// Diagnostics (tools/bench_gbuffer.py): the accelerated geometry-buffer kernel walks per lane
+// (walk 1) instead of as packets (0), with `waves` tiles to a block (1, 2 or 4; 0 = default).
+// Same planes either way.
+extern "C" int rt_debug_gbuffer(rt_ctx* c, int walk, int waves) {
+    if (!c || (walk != 0 && walk != 1) || (waves != 0 && waves != 1 && waves != 2 && waves != 4)) return RT_ERR_INVALID;
+    c->gbuf_walk = walk;
+    c->gbuf_waves = waves;
     return RT_OK;
 }
 

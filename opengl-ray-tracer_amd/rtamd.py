@@ -98,6 +98,17 @@ class rt_params(C.Structure):
                 ("useFresnel", C.c_int), ("useMollerTrumbore", C.c_int)]
 
 
+class rt_gbuffer(C.Structure):
+    """The planes of a geometry buffer (include/rt_api.h): pointer and pitch in bytes each,
+    a null pointer = plane not wanted."""
+    _fields_ = [("shape", C.c_void_p), ("shape_pitch", C.c_size_t), ("depth", C.c_void_p), ("depth_pitch", C.c_size_t),
+                ("normal", C.c_void_p), ("normal_pitch", C.c_size_t), ("position", C.c_void_p),
+                ("position_pitch", C.c_size_t)]
+
+
+GBUFFER_PLANES = ("shape", "depth", "normal", "position")
+
+
 class rt_accel_info(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("built", "local_nodes", "local_leaves", "bounded_prims", "always_prims",
                                        "max_stack", "last_kernel", "scene_tree", "scene_nodes", "scene_items",
@@ -244,6 +255,8 @@ RT_SYMBOLS = {
     "rt_trace_rays": (_I, [_P, _P, _I, _P, _I]),
     "rt_trace_rays_host": (_I, [_P, _P, _I, _P, _I]),
     "rt_trace_pixels": (_I, [_P, _I, _I, _P, _I, _P]),
+    "rt_dispatch_gbuffer": (_I, [_P, _I, _I, _I, _I, _I, _I, _P]),
+    "rt_gbuffer_host": (_I, [_P, _I, _I, _P]),
     "rt_status_string": (C.c_char_p, [_I]),
 }
 
@@ -834,6 +847,43 @@ class ComputeShader:
         self._chk(self._lib.rt_trace_pixels(self._h, int(width), int(height), _ptr(xy), len(xy), _ptr(hits)),
                   "rt_trace_pixels")
         return hits["shape"].copy(), hits["distance"].copy(), hits["occluded"].copy()
+
+    def gbuffer(self, width, height, planes=GBUFFER_PLANES):
+        """rt_gbuffer_host: the geometry buffer of the whole width x height frame as a dict of
+        numpy arrays: "shape" [H, W] int32 (-1 on a miss), "depth" [H, W] float32 (1e20 on a
+        miss), "normal" and "position" [H, W, 4] float32 (position's w is 1 on a hit, 0 on a
+        miss). planes: which of them to compute."""
+        out, g = {}, rt_gbuffer()
+        for name in planes:
+            if name not in GBUFFER_PLANES:
+                raise ValueError(f"gbuffer: unknown plane {name!r}")
+            a = np.empty((height, width) if name in ("shape", "depth") else (height, width, 4),
+                         np.int32 if name == "shape" else np.float32)
+            out[name] = a
+            setattr(g, name, a.ctypes.data)
+            setattr(g, name + "_pitch", a.strides[0])
+        self._chk(self._lib.rt_gbuffer_host(self._h, int(width), int(height), C.byref(g)), "rt_gbuffer_host")
+        return out
+
+    def gbuffer_device(self, width, height, y0, stripe, period, out_rows, shape=None, depth=None, normal=None,
+                       position=None):
+        """rt_dispatch_gbuffer: compact rows as dispatch_rows_ex; each plane a (device pointer,
+        pitch in bytes) pair or None. Stream-ordered, asynchronous."""
+        g = rt_gbuffer()
+        for name, plane in (("shape", shape), ("depth", depth), ("normal", normal), ("position", position)):
+            if plane is not None:
+                setattr(g, name, plane[0])
+                setattr(g, name + "_pitch", plane[1])
+        self._chk(self._lib.rt_dispatch_gbuffer(self._h, int(width), int(height), int(y0), int(stripe), int(period),
+                                                int(out_rows), C.byref(g)), "rt_dispatch_gbuffer")
+
+    def debug_gbuffer(self, walk=0, waves=0):
+        """Diagnostics: the accelerated geometry-buffer kernel walks per lane (walk 1) instead of
+        as packets, with `waves` 8x8 tiles to a block (0: default). Same planes either way."""
+        fn = self._lib.rt_debug_gbuffer
+        fn.argtypes = [_P, _I, _I]
+        fn.restype = _I
+        self._chk(fn(self._h, int(walk), int(waves)), "rt_debug_gbuffer")
 
     def debug_ss_general(self, on):
         """Diagnostics: supersampled frames render the sample frame and filter it with a second
