@@ -567,6 +567,78 @@ int rt_dispatch_gbuffer(struct rt_ctx* ctx, int width, int height, int y0, int s
  * as above. */
 int rt_gbuffer_host(struct rt_ctx* ctx, int width, int height, const rt_gbuffer* host_out);
 
+/* Ambient occlusion: per pixel, how many of `rays` fixed hemisphere rays about the visible
+ * surface's normal are blocked within `radius`. A host multiplies its ambient term by the
+ * visibility plane. One kernel of its own finds the camera hit, builds the
+ * rays and walks them; no ray, hit or geometry plane crosses the bus. Nothing in a frame
+ * dispatch changes: applying the term is the host's.
+ *
+ * Planes, rows, what applies, what does not enter, pending updates and what is left alone:
+ * exactly as rt_dispatch_gbuffer above (rows y(r) >= height untouched; of a row only the first
+ * `width` pixels are written, `width` bytes of count and 4*width bytes of visibility, not one
+ * byte after them). With rt_set_samples(n) the planes describe sample (0, 0).
+ *
+ * Definition of a pixel. Every operation is float32, in the order written, none contracted.
+ * Take rt_dispatch_gbuffer's values of pixel (x, y): shape, position p and normal n; and the
+ * camera ray's direction d as a dispatch generates it. A miss (shape -1) has count 0 and
+ * visibility 1.0f. Otherwise:
+ *  1. Facing. s = (n.x*d.x + n.y*d.y) + n.z*d.z; nf = s > 0 ? -n : n (a NaN keeps n).
+ *  2. Frame. sg = copysignf(1, nf.z); a = -1.0f / (sg + nf.z); b = (nf.x*nf.y)*a;
+ *       t = (1.0f + sg*((nf.x*nf.x)*a), sg*b, -(sg*nf.x));
+ *       u = (b, sg + (nf.y*nf.y)*a, -nf.y).
+ *  3. Tables (csrc/ao_table.h, written by tools/gen_ao_table.py, returned by rt_ao_table; the
+ *     tables are the definition, as the thresholds are for RT_FORMAT_SRGBA8).
+ *       D[k], k = 0..63: cosine-weighted Halton points; with u1 the radical inverse of k + 1 in
+ *       base 2 and u2 that in base 3, D[k] = (sqrt(u1) cos 2 pi u2, sqrt(u1) sin 2 pi u2,
+ *       sqrt(1 - u1)) in double, rounded to float32. Ray count K uses D[0..K-1].
+ *       ROT[j], j = 0..15: (cos, sin) of 2 pi ((7 j) mod 16) / 16 in double, rounded to float32.
+ *  4. Rotation per pixel (interleaved sampling; a 4x4 blur by the host removes the pattern).
+ *     j = (x & 3) + 4*(y & 3) on image coordinates, (c, sn) = ROT[j];
+ *       lx = c*D[k].x - sn*D[k].y; ly = sn*D[k].x + c*D[k].y; lz = D[k].z.
+ *  5. Ray k. Origin p + nf*bias per component (one multiply, one add: the shader's shadow
+ *     origin); direction per component (t.c*lx + u.c*ly) + nf.c*lz; limit radius.
+ *  6. count = the number of k < rays whose ray is occluded in the sense of RT_TRACE_ANY: an
+ *     INNER hit nearer than min(radius, 1e20f). visibility = (float)(rays - count) /
+ *     (float)rays, one IEEE division.
+ * Every value is exact: the same bytes from every kernel variant, and count equals the sum of
+ * rt_trace_rays(RT_TRACE_ANY) over these rays.
+ *
+ * Errors, returned before anything is launched. RT_ERR_INVALID: everything
+ * rt_dispatch_gbuffer refuses about ctx, width, height, y0, stripe, period and out_rows;
+ * params or out NULL; rays outside 1..64; radius NaN or <= 0 (+inf is allowed); bias NaN,
+ * negative or infinite; reserved != 0; both planes NULL; count_pitch < width; a visibility
+ * pointer or pitch not 4-byte aligned, or visibility_pitch < 4*width. RT_ERR_NO_SCENE as for
+ * the geometry buffer. out_rows == 0 is RT_OK and launches nothing. */
+typedef struct rt_ao_params {
+    int rays;        /* K, 1..64 */
+    float radius;    /* occlusion distance, > 0, may be +inf */
+    float bias;      /* origin offset along the facing normal, >= 0, finite */
+    int reserved;    /* 0 */
+} rt_ao_params;
+
+typedef struct rt_ao {               /* planes; a NULL pointer = plane not wanted, at least one */
+    uint8_t* count;      size_t count_pitch;       /* 1 B / pixel: occluded rays, 0..rays */
+    float*   visibility; size_t visibility_pitch;  /* 4 B / pixel: (float)(rays - count) / (float)rays */
+} rt_ao;
+
+RT_STATIC_ASSERT(sizeof(rt_ao_params) == 16 && offsetof(rt_ao_params, radius) == 4 &&
+                 offsetof(rt_ao_params, bias) == 8 && offsetof(rt_ao_params, reserved) == 12, "rt_ao_params");
+RT_STATIC_ASSERT(sizeof(rt_ao) == 4 * sizeof(void*) && offsetof(rt_ao, count_pitch) == sizeof(void*) &&
+                 offsetof(rt_ao, visibility) == 2 * sizeof(void*) &&
+                 offsetof(rt_ao, visibility_pitch) == 3 * sizeof(void*), "rt_ao");
+
+/* Device pointers; stream-ordered on the context's stream, asynchronous. */
+int rt_dispatch_ao(struct rt_ctx* ctx, int width, int height, int y0, int stripe, int period, int out_rows,
+                   const rt_ao_params* params, const rt_ao* out);
+
+/* Host pointers, the whole frame (rows [0, height)), staged through buffers the context keeps
+ * between calls; returns when the planes are in host memory. Checked as above. */
+int rt_ao_host(struct rt_ctx* ctx, int width, int height, const rt_ao_params* params, const rt_ao* host_out);
+
+/* The defining tables: D as 64 x 3 floats, ROT as 16 x 2; either pointer may be NULL. Needs no
+ * device and no context. */
+int rt_ao_table(float* dirs64x3, float* rot16x2);
+
 /* Accelerator statistics for the uploaded scene. */
 int rt_accel_info_get(struct rt_ctx* ctx, rt_accel_info* out);
 

@@ -43,6 +43,9 @@
 //       hit of every pixel's camera ray as planes of shape, depth, normal and position. One
 //       8x8 tile per wave through packet_walk (or lane_walk for a camera beyond the
 //       accelerator's origin bound); k_gbuffer_ref is k_lane's literal walk.
+//   k_ao<MT, LANE, PACK> / k_ao_ref : ambient occlusion (rt_dispatch_ao): k_gbuffer's camera
+//       walk, then each hit pixel's K hemisphere rays through the shadow form of lane_walk,
+//       per hit lane or (PACK) repacked over the wave's 64 lanes; one byte per pixel out.
 //   k_tile_order / k_cost_dilate : the next frame's dispatch order from the tile
 //       costs a k_accel dispatch recorded (rt_set_schedule).
 //   k_refit / k_inf_slots : boxes and cones of moved shapes (rt_animate,
@@ -74,6 +77,7 @@
 #include "accel_math.h"
 #include "lbvh.h"
 #include "rt_device.h"
+#include "ao_table.h"
 #include "group_wait.h"
 #include "rt_internal.h"
 
@@ -2222,6 +2226,189 @@ __global__ __launch_bounds__(kBlock) void k_gbuffer_ref(rt_gbuffer g, KParams kp
     store_gbuffer(g, pc.r, pc.x, rec.idx, h.d, shape_normal(rec, h.p), h.p, 1.0f);
 }
 
+// ---------------------------------------------------------------------------
+// Ambient occlusion (rt_dispatch_ao / rt_ao_host): per pixel the number of the K fixed
+// hemisphere rays about the visible surface's facing normal that are occluded within a radius
+// (include/rt_api.h, "Definition of a pixel": every operation below is in that order).
+
+__device__ const float kAoDir[64 * 3] = {RT_AO_DIRS};
+__device__ const float kAoRot[16 * 2] = {RT_AO_ROT};
+
+struct AoArgs {
+    rt_ao out;
+    int rays;
+    float radius, bias;
+};
+
+// Steps 1, 2 and 5's origin: the facing normal, the tangent frame about it, the rays' origin.
+struct AoFrame {
+    V o, t, u, nf;
+};
+
+__device__ __forceinline__ AoFrame ao_frame(V p, V n, V d, float bias) {
+    const float s = (n.x * d.x + n.y * d.y) + n.z * d.z;
+    const V nf = s > 0.0f ? -n : n;
+    const float sg = copysignf(1.0f, nf.z);
+    const float a = -1.0f / (sg + nf.z);
+    const float b = (nf.x * nf.y) * a;
+    AoFrame f;
+    f.t = mk(1.0f + sg * ((nf.x * nf.x) * a), sg * b, -(sg * nf.x));
+    f.u = mk(b, sg + (nf.y * nf.y) * a, -nf.y);
+    f.nf = nf;
+    f.o = p + nf * bias;
+    return f;
+}
+
+// Steps 4 and 5: ray k of a pixel whose rotation is (c, sn).
+__device__ __forceinline__ Ray ao_ray(const AoFrame& f, float c, float sn, int k) {
+    const float dx = kAoDir[3 * k], dy = kAoDir[3 * k + 1], lz = kAoDir[3 * k + 2];
+    const float lx = c * dx - sn * dy, ly = sn * dx + c * dy;
+    return Ray{f.o, mk((f.t.x * lx + f.u.x * ly) + f.nf.x * lz, (f.t.y * lx + f.u.y * ly) + f.nf.y * lz,
+                       (f.t.z * lx + f.u.z * ly) + f.nf.z * lz)};
+}
+
+// One pixel of the planes the caller gave: a byte store, and a streaming dword store.
+__device__ __forceinline__ void store_ao(const AoArgs& q, int r, int x, int count) {
+    const size_t row = static_cast<size_t>(r);
+    if (q.out.count) (q.out.count + row * q.out.count_pitch)[x] = static_cast<uint8_t>(count);
+    if (q.out.visibility)
+        __builtin_nontemporal_store(
+            static_cast<float>(q.rays - count) / static_cast<float>(q.rays),
+            reinterpret_cast<float*>(reinterpret_cast<char*>(q.out.visibility) + row * q.out.visibility_pitch) + x);
+}
+
+constexpr int kAoSlot = 15;  // dwords a hit lane leaves in LDS (PACK): o, t, u, nf, (c, sn), its counter
+
+// One 8x8 tile per wave, any number of waves to a block. The camera rays go exactly as in
+// k_gbuffer (the root-box skip, then packet_walk, or LANE: lane_walk). The occlusion rays go
+// through the shadow form of lane_walk with k_trace's LDS stacks.
+//   PACK = false (the default, kAoPack): each hit lane walks its own K rays, one after the
+//     other. A tile on a silhouette keeps its miss lanes idle for K walks.
+//   PACK = true: the h hit lanes (a ballot) leave their frame in LDS, slot = rank among the hit
+//     lanes; the wave walks the h * K work items 64 at a time (item i: ray i / h of slot i % h,
+//     so the lanes of a round walk the same or neighbouring k of neighbouring pixels) and adds
+//     each occluded ray to its owner's LDS counter. ceil(h * K / 64) rounds, none for a tile
+//     without a hit.
+// Dynamic LDS: lane_stack x 6 B per lane, then, PACK, kAoSlot x 256 B per wave. Waves do not
+// share LDS, so nothing here waits on a block barrier.
+template <bool MT, bool LANE, bool PACK>
+__global__ __launch_bounds__(kBlock) void k_ao(AccelPtrs A, AoArgs q, KParams kp) {
+    extern __shared__ int lds_stack[];
+    const int tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (tile >= kp.tiles) return;  // wave-uniform
+    int* stk = lds_stack + threadIdx.x;
+    unsigned short* stt =
+        reinterpret_cast<unsigned short*>(lds_stack + static_cast<size_t>(kp.lane_stack) * blockDim.x) + threadIdx.x;
+    const PixelCoord pc = tile_pixel(kp, tile);
+    const Ray ray = primary_ray(kp, pc.x, pc.y);
+    bool alive = pc.active;
+    if (kp.root_ok) {
+        V rlo = mk(kp.root_lo[0], kp.root_lo[1], kp.root_lo[2]), rhi = mk(kp.root_hi[0], kp.root_hi[1], kp.root_hi[2]);
+        if (kp.root_ok == 2) {
+            const float4 a = A.anodes[4 * static_cast<size_t>(A.N - 1)], b = A.anodes[4 * static_cast<size_t>(A.N - 1) + 1];
+            rlo = mk(a.x, a.y, a.z);
+            rhi = mk(b.x, b.y, b.z);
+        }
+        alive = alive && ray_aabb(ray.o, inv_dir(ray.d), rlo, rhi);
+    }
+    Best best{1e20f, 0x7fffffff, 0.f, -1};
+    bool unused = false;
+    WalkCount wc{0u, 0u, 0u, 0u};
+    if (LANE) {
+        lane_walk<false, false, false, MT, true>(A, ray, alive, 0.f, best, unused, stk, stt, blockDim.x,
+                                                 kp.lane_stack, wc);
+    } else {
+        packet_walk<false, false, false, MT>(A, ray, alive, 0.f, best, unused, wc);
+    }
+    const bool hit = pc.active && best.slot >= 0;
+    const unsigned long long hm = __ballot(hit);
+    if (hm == 0) {  // wave-uniform: a tile of misses costs the camera walk only
+        if (pc.active) store_ao(q, pc.r, pc.x, 0);
+        return;
+    }
+    AoFrame f{};
+    float c = 1.0f, sn = 0.0f;
+    if (hit) {
+        const V p = hit_point(ray, best.t);
+        f = ao_frame(p, shape_normal(load_prim(A.prims, best.slot), p), ray.d, q.bias);
+        const int j = (pc.x & 3) + 4 * (pc.y & 3);
+        c = kAoRot[2 * j];
+        sn = kAoRot[2 * j + 1];
+    }
+    const float lim = gmin(q.radius, 1e20f);
+    int count = 0;
+    if (!PACK) {
+        for (int k = 0; k < q.rays; ++k) {  // wave-uniform trip count
+            bool occluded = false;
+            Best b{1e20f, 0x7fffffff, 0.f, -1};
+            lane_walk<true, false, false, MT, true>(A, ao_ray(f, c, sn, k), hit, lim, b, occluded, stk, stt,
+                                                    blockDim.x, kp.lane_stack, wc);
+            count += occluded ? 1 : 0;
+        }
+    } else {
+        const int lane = threadIdx.x & 63;
+        float* fr = reinterpret_cast<float*>(lds_stack) + (static_cast<size_t>(kp.lane_stack) * blockDim.x * 6) / 4 +
+                    static_cast<size_t>(threadIdx.x >> 6) * (kAoSlot * 64);
+        int* cnt = reinterpret_cast<int*>(fr) + 14 * 64;
+        const int h = __popcll(hm);
+        const int slot = __popcll(hm & ((1ull << lane) - 1ull));
+        if (hit) {
+            const float v[14] = {f.o.x, f.o.y, f.o.z, f.t.x, f.t.y, f.t.z, f.u.x, f.u.y, f.u.z, f.nf.x, f.nf.y, f.nf.z, c, sn};
+#pragma unroll
+            for (int e = 0; e < 14; ++e) fr[e * 64 + slot] = v[e];
+            cnt[slot] = 0;
+        }
+        // the wave's own LDS writes, read by its other lanes: program order, no block barrier
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const unsigned items = static_cast<unsigned>(h) * static_cast<unsigned>(q.rays);  // at most 4096
+        for (unsigned base = 0; base < items; base += 64) {  // wave-uniform
+            const unsigned i = base + static_cast<unsigned>(lane);
+            const bool on = i < items;
+            const unsigned k = on ? i / static_cast<unsigned>(h) : 0u;
+            const int j = on ? static_cast<int>(i - k * static_cast<unsigned>(h)) : 0;
+            AoFrame g;
+            g.o = mk(fr[0 * 64 + j], fr[1 * 64 + j], fr[2 * 64 + j]);
+            g.t = mk(fr[3 * 64 + j], fr[4 * 64 + j], fr[5 * 64 + j]);
+            g.u = mk(fr[6 * 64 + j], fr[7 * 64 + j], fr[8 * 64 + j]);
+            g.nf = mk(fr[9 * 64 + j], fr[10 * 64 + j], fr[11 * 64 + j]);
+            bool occluded = false;
+            Best b{1e20f, 0x7fffffff, 0.f, -1};
+            lane_walk<true, false, false, MT, true>(A, ao_ray(g, fr[12 * 64 + j], fr[13 * 64 + j], static_cast<int>(k)),
+                                                    on, lim, b, occluded, stk, stt, blockDim.x, kp.lane_stack, wc);
+            if (on && occluded) atomicAdd(&cnt[j], 1);  // LDS atomic
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (hit) count = cnt[slot];
+    }
+    if (pc.active) store_ao(q, pc.r, pc.x, count);
+}
+
+// The same planes from k_lane's literal walks over the reference tree alone (contexts without
+// a usable accelerator, RT_KERNEL_LANE / RT_KERNEL_PACKET): k_lane's blocks, pixels and stacks;
+// lane_closest_bvh for the camera ray, then lane_any_bvh for each of the K rays.
+__global__ __launch_bounds__(kBlock) void k_ao_ref(AoArgs q, KParams kp) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    const PixelCoord pc = pixel_of(kp);
+    if (!pc.active) return;
+    const Ray r = primary_ray(kp, pc.x, pc.y);
+    Counters cn;
+    const LaneHit h = lane_closest_bvh<false>(kp, kp.nodes, kp.geo_leaf, r, stk, cn);
+    int count = 0;
+    if (h.found) {
+        const AoFrame f = ao_frame(h.p, shape_normal(load_rec(kp.geo_leaf, h.slot), h.p), r.d, q.bias);
+        const int j = (pc.x & 3) + 4 * (pc.y & 3);
+        const float c = kAoRot[2 * j], sn = kAoRot[2 * j + 1], lim = gmin(q.radius, 1e20f);
+        for (int k = 0; k < q.rays; ++k)
+            count += lane_any_bvh(kp, kp.nodes, kp.geo_leaf, ao_ray(f, c, sn, k), lim, stk) ? 1 : 0;
+    }
+    store_ao(q, pc.r, pc.x, count);
+}
+
 // The general path of rt_set_samples: the sample frame was rendered by any kernel into a
 // scratch surface (compact rows, RGBA32F); one thread per output pixel applies the box
 // filter in the order rt_api.h fixes -- log2 N pairwise rounds along x, then along y,
@@ -3302,6 +3489,11 @@ struct rt_ctx {
     size_t gbuf_stage_cap = 0;
     int gbuf_walk = 0;    // rt_debug_gbuffer: 1 = the accelerated form walks per lane (diagnostics)
     int gbuf_waves = 0;   // rt_debug_gbuffer: waves (tiles) per block, 0 = the default
+    // rt_ao_host: staging for the two planes, grown on demand and kept between calls
+    float* ao_stage = nullptr;
+    size_t ao_stage_cap = 0;
+    int ao_form = 0;      // rt_debug_ao: 0 = the default form (per hit lane), 1 = repacked, 2 = per hit lane
+    int ao_waves = 0;     // rt_debug_ao: waves (tiles) per block, 0 = the default
     int kernel = RT_KERNEL_AUTO;
     int last_kind = 0;
     // own surface
@@ -5582,16 +5774,10 @@ int gbuffer_check(const rt_ctx* c, int width, int height, int y0, int stripe, in
     return RT_OK;
 }
 
-// One geometry-buffer launch on the context's stream: pending scene writes first, as one
-// refit (query_target); then k_gbuffer over the accelerator a query would walk -- as packets
-// while the camera lies inside its origin bound, per lane beyond it -- or k_gbuffer_ref's
-// literal walk. Like a query it touches none of the render state.
-int gbuffer_launch(rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows,
-                   const rt_gbuffer& g) {
-    rt_ctx* t = c;
-    bool accel = false;
-    if (const int rc = query_target(c, &t, &accel)) return rc;
-    const bool mt = c->params.useMollerTrumbore != 0;
+// The kernel parameters of a geometry-buffer or ambient-occlusion launch over target t: the
+// scene, the stacks, the camera and the row mapping; nothing of the shading.
+KParams plane_params(const rt_ctx* c, const rt_ctx* t, int width, int height, int y0, int stripe, int period,
+                     int out_rows) {
     KParams kp;
     std::memset(&kp, 0, sizeof kp);
     kp.geo_leaf = t->geo_leaf;
@@ -5602,7 +5788,7 @@ int gbuffer_launch(rt_ctx* c, int width, int height, int y0, int stripe, int per
     kp.I = t->I;
     kp.max_stack = t->max_stack < 1 ? 1 : t->max_stack;
     kp.useBVH = 1;
-    kp.useMT = mt ? 1 : 0;
+    kp.useMT = c->params.useMollerTrumbore != 0 ? 1 : 0;
     kp.lane_stack = t->lane_stack_override > 0 ? t->lane_stack_override : t->accel.max_stack;
     fill_camera(c->cam, kp);
     kp.resX = c->params.resX;
@@ -5615,14 +5801,11 @@ int gbuffer_launch(rt_ctx* c, int width, int height, int y0, int stripe, int per
     kp.out_rows = out_rows;
     kp.tiles_x = (width + 7) / 8;
     kp.tiles = kp.tiles_x * ((out_rows + 7) / 8);
-    if (!accel) {
-        const dim3 grid((width + kTileW - 1) / kTileW, (out_rows + kTileH - 1) / kTileH);
-        const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
-        hipLaunchKernelGGL(k_gbuffer_ref, grid, dim3(kBlock), lds, c->stream, g, kp);
-        HIP_TRY(hipGetLastError());
-        return RT_OK;
-    }
-    // the root's current bounds, as launch() passes them to k_accel
+    return kp;
+}
+
+// The root's current bounds, as launch() passes them to k_accel (the tile kernels' sky skip).
+void plane_root(const rt_ctx* t, KParams& kp) {
     if (kp.N > 0 && t->nodes_on_device_newer) kp.root_ok = 2;
     if (kp.N > 0 && !t->nodes_on_device_newer && static_cast<int>(t->host_nodes.size()) == kp.N) {
         const FlatNode& rn = t->host_nodes[kp.N - 1];
@@ -5634,6 +5817,27 @@ int gbuffer_launch(rt_ctx* c, int width, int height, int y0, int stripe, int per
         kp.root_hi[1] = rn.boundsMax.y;
         kp.root_hi[2] = rn.boundsMax.z;
     }
+}
+
+// One geometry-buffer launch on the context's stream: pending scene writes first, as one
+// refit (query_target); then k_gbuffer over the accelerator a query would walk -- as packets
+// while the camera lies inside its origin bound, per lane beyond it -- or k_gbuffer_ref's
+// literal walk. Like a query it touches none of the render state.
+int gbuffer_launch(rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows,
+                   const rt_gbuffer& g) {
+    rt_ctx* t = c;
+    bool accel = false;
+    if (const int rc = query_target(c, &t, &accel)) return rc;
+    const bool mt = c->params.useMollerTrumbore != 0;
+    KParams kp = plane_params(c, t, width, height, y0, stripe, period, out_rows);
+    if (!accel) {
+        const dim3 grid((width + kTileW - 1) / kTileW, (out_rows + kTileH - 1) / kTileH);
+        const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
+        hipLaunchKernelGGL(k_gbuffer_ref, grid, dim3(kBlock), lds, c->stream, g, kp);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    }
+    plane_root(t, kp);
     // the packet form needs the shared origin inside the accelerator's bound (accel_usable)
     const float cmag = std::max({std::fabs(kp.cam_pos.x), std::fabs(kp.cam_pos.y), std::fabs(kp.cam_pos.z)});
     const bool lane = c->gbuf_walk == 1 || !(cmag <= t->accel.origin_lim);
@@ -5645,6 +5849,73 @@ int gbuffer_launch(rt_ctx* c, int width, int height, int y0, int stripe, int per
                     : (mt ? k_gbuffer<true, false> : k_gbuffer<false, false>);
     const size_t lds = lane ? static_cast<size_t>(kp.lane_stack) * block.x * 6 : 0;  // the packet form: no LDS
     hipLaunchKernelGGL(kfn, grid, block, lds, c->stream, accel_ptrs(t), g, kp);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// Ambient occlusion. The checks of rt_dispatch_ao and rt_ao_host (include/rt_api.h), before
+// anything is launched; RT_OK with *run = false when there is nothing to launch.
+// The default form: per hit lane. It measured 5-23 % faster than the repacked form in 17 of the
+// 18 rows of tools/bench_ao.py (three scenes, K = 4, 16, 64, radius 2.0 and +inf) and equal in
+// one (DESIGN.md §4 "Ambient occlusion"): most tiles of those frames are all hits or all sky,
+// where repacking only adds its LDS traffic. Tiles per block: one; two and four measured equal or slower.
+constexpr bool kAoPack = false;
+constexpr int kAoWaves = 1;
+
+int ao_check(const rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows,
+             const rt_ao_params* p, const rt_ao* out, bool* run) {
+    *run = false;
+    if (!c || !p || !out || (!out->count && !out->visibility)) return RT_ERR_INVALID;
+    if (!c->have_scene || !c->have_cam || !c->have_params) return RT_ERR_NO_SCENE;
+    if (width <= 0 || height <= 0 || stripe <= 0 || period < stripe || out_rows < 0 || y0 < 0) return RT_ERR_INVALID;
+    if (p->rays < 1 || p->rays > 64 || !(p->radius > 0.0f) || !(p->bias >= 0.0f) || std::isinf(p->bias) ||
+        p->reserved != 0)
+        return RT_ERR_INVALID;
+    if (out->count && out->count_pitch < static_cast<size_t>(width)) return RT_ERR_INVALID;
+    if (out->visibility && (out->visibility_pitch < static_cast<size_t>(width) * 4 || out->visibility_pitch % 4 != 0 ||
+                            reinterpret_cast<uintptr_t>(out->visibility) % 4 != 0))
+        return RT_ERR_INVALID;
+    if ((static_cast<long long>(out_rows) + kTileH - 1) / kTileH > 65535 ||
+        static_cast<unsigned long long>(width) * static_cast<unsigned long long>(out_rows) >= (1ull << 32))
+        return RT_ERR_INVALID;
+    *run = out_rows > 0;
+    return RT_OK;
+}
+
+// One ambient-occlusion launch on the context's stream, set up as gbuffer_launch: the same
+// target, parameters and camera-walk choice; k_ao's LDS is the lane stacks of its occlusion
+// walks (always) and, repacked (rt_debug_ao form 1), 15 dwords per lane for the hit lanes'
+// frames and counters.
+int ao_launch(rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows, const rt_ao_params& p,
+              const rt_ao& out) {
+    rt_ctx* t = c;
+    bool accel = false;
+    if (const int rc = query_target(c, &t, &accel)) return rc;
+    const bool mt = c->params.useMollerTrumbore != 0;
+    KParams kp = plane_params(c, t, width, height, y0, stripe, period, out_rows);
+    const AoArgs q{out, p.rays, p.radius, p.bias};
+    if (!accel) {
+        const dim3 grid((width + kTileW - 1) / kTileW, (out_rows + kTileH - 1) / kTileH);
+        const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
+        hipLaunchKernelGGL(k_ao_ref, grid, dim3(kBlock), lds, c->stream, q, kp);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    }
+    plane_root(t, kp);
+    const float cmag = std::max({std::fabs(kp.cam_pos.x), std::fabs(kp.cam_pos.y), std::fabs(kp.cam_pos.z)});
+    const bool lane = !(cmag <= t->accel.origin_lim);
+    const bool pack = c->ao_form == 0 ? kAoPack : c->ao_form == 1;
+    const size_t per_wave = static_cast<size_t>(kp.lane_stack) * 64 * 6 + (pack ? kAoSlot * 64 * sizeof(int) : 0);
+    int waves = c->ao_waves > 0 ? c->ao_waves : kAoWaves;
+    while (waves > 1 && per_wave * waves > 65536) waves /= 2;  // within the 64 KB a block may ask for
+    const dim3 grid((kp.tiles + waves - 1) / waves), block(64 * waves);
+    auto pick = [&](auto m, auto l) {
+        return pack ? k_ao<decltype(m)::value, decltype(l)::value, true> : k_ao<decltype(m)::value, decltype(l)::value, false>;
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    auto kfn = mt ? (lane ? pick(T{}, T{}) : pick(T{}, F{})) : (lane ? pick(F{}, T{}) : pick(F{}, F{}));
+    hipLaunchKernelGGL(kfn, grid, block, per_wave * waves, c->stream, accel_ptrs(t), q, kp);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -5805,6 +6076,7 @@ int rt_destroy(rt_ctx* c) {
     hipFree(c->trace_in);
     hipFree(c->trace_hits);
     hipFree(c->gbuf_stage);
+    hipFree(c->ao_stage);
     hipFree(c->tail_queue);
     hipFree(c->tail_counts);
     hipFree(c->tile_times);
@@ -6476,6 +6748,48 @@ int rt_gbuffer_host(rt_ctx* c, int width, int height, const rt_gbuffer* host_out
     return RT_OK;
 }
 
+int rt_dispatch_ao(rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows,
+                   const rt_ao_params* params, const rt_ao* out) {
+    bool run;
+    if (const int rc = ao_check(c, width, height, y0, stripe, period, out_rows, params, out, &run)) return rc;
+    if (!run) return RT_OK;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    return ao_launch(c, width, height, y0, stripe, period, out_rows, *params, *out);
+}
+
+int rt_ao_host(rt_ctx* c, int width, int height, const rt_ao_params* params, const rt_ao* host_out) {
+    bool run;
+    if (const int rc = ao_check(c, width, height, 0, 1, 1, height, params, host_out, &run)) return rc;
+    if (!run) return RT_OK;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    // visibility first (4-byte rows), then count, rows packed
+    const size_t px = static_cast<size_t>(width) * static_cast<size_t>(height);
+    const size_t need = (host_out->visibility ? px : 0) + (host_out->count ? (px + 3) / 4 : 0);
+    if (const int rc = ensure_staging(c->ao_stage, c->ao_stage_cap, need)) return rc;
+    rt_ao dev{};
+    const size_t w1 = static_cast<size_t>(width), w4 = w1 * 4;
+    float* at = c->ao_stage;
+    if (host_out->visibility) dev.visibility = at, dev.visibility_pitch = w4, at += px;
+    if (host_out->count) dev.count = reinterpret_cast<uint8_t*>(at), dev.count_pitch = w1;
+    if (const int rc = ao_launch(c, width, height, 0, 1, 1, height, *params, dev)) return rc;
+    if (host_out->visibility)
+        HIP_TRY(hipMemcpy2DAsync(host_out->visibility, host_out->visibility_pitch, dev.visibility, w4, w4,
+                                 static_cast<size_t>(height), hipMemcpyDeviceToHost, c->stream));
+    if (host_out->count)
+        HIP_TRY(hipMemcpy2DAsync(host_out->count, host_out->count_pitch, dev.count, w1, w1,
+                                 static_cast<size_t>(height), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(sync_stream(c));
+    return RT_OK;
+}
+
+int rt_ao_table(float* dirs64x3, float* rot16x2) {
+    static const float d[64 * 3] = {RT_AO_DIRS};
+    static const float r[16 * 2] = {RT_AO_ROT};
+    if (dirs64x3) std::memcpy(dirs64x3, d, sizeof d);
+    if (rot16x2) std::memcpy(rot16x2, r, sizeof r);
+    return RT_OK;
+}
+
 }  // extern "C"
 
 extern "C" int rt_accel_info_get(rt_ctx* c, rt_accel_info* out) {
@@ -6723,6 +7037,16 @@ extern "C" int rt_debug_gbuffer(rt_ctx* c, int walk, int waves) {
     if (!c || (walk != 0 && walk != 1) || (waves != 0 && waves != 1 && waves != 2 && waves != 4)) return RT_ERR_INVALID;
     c->gbuf_walk = walk;
     c->gbuf_waves = waves;
+    return RT_OK;
+}
+
+// Diagnostics (tools/bench_ao.py): the accelerated ambient-occlusion kernel walks its rays
+// repacked over the wave (form 1) or per hit lane (form 2; 0 = the default form), with `waves`
+// tiles to a block (1, 2 or 4; 0 = default). Same planes either way.
+extern "C" int rt_debug_ao(rt_ctx* c, int form, int waves) {
+    if (!c || form < 0 || form > 2 || (waves != 0 && waves != 1 && waves != 2 && waves != 4)) return RT_ERR_INVALID;
+    c->ao_form = form;
+    c->ao_waves = waves;
     return RT_OK;
 }
 

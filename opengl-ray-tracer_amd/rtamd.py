@@ -109,6 +109,22 @@ class rt_gbuffer(C.Structure):
 GBUFFER_PLANES = ("shape", "depth", "normal", "position")
 
 
+class rt_ao_params(C.Structure):
+    """rt_dispatch_ao's parameters (include/rt_api.h): rays 1..64, radius > 0 (may be inf),
+    bias >= 0, reserved 0."""
+    _fields_ = [("rays", C.c_int), ("radius", C.c_float), ("bias", C.c_float), ("reserved", C.c_int)]
+
+
+class rt_ao(C.Structure):
+    """The planes of an ambient-occlusion dispatch: pointer and pitch in bytes each, a null
+    pointer = plane not wanted."""
+    _fields_ = [("count", C.c_void_p), ("count_pitch", C.c_size_t), ("visibility", C.c_void_p),
+                ("visibility_pitch", C.c_size_t)]
+
+
+AO_PLANES = ("count", "visibility")
+
+
 class rt_accel_info(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("built", "local_nodes", "local_leaves", "bounded_prims", "always_prims",
                                        "max_stack", "last_kernel", "scene_tree", "scene_nodes", "scene_items",
@@ -257,6 +273,9 @@ RT_SYMBOLS = {
     "rt_trace_pixels": (_I, [_P, _I, _I, _P, _I, _P]),
     "rt_dispatch_gbuffer": (_I, [_P, _I, _I, _I, _I, _I, _I, _P]),
     "rt_gbuffer_host": (_I, [_P, _I, _I, _P]),
+    "rt_dispatch_ao": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "rt_ao_host": (_I, [_P, _I, _I, _P, _P]),
+    "rt_ao_table": (_I, [_P, _P]),
     "rt_status_string": (C.c_char_p, [_I]),
 }
 
@@ -322,6 +341,16 @@ def rt_lib():
     if _rt_lib is None:
         _rt_lib = _bind(_bind(_load("librtamd.so"), RT_SYMBOLS), GROUP_SYMBOLS)
     return _rt_lib
+
+
+def ao_table():
+    """rt_ao_table: the tables that define rt_dispatch_ao's rays, (D [64, 3], ROT [16, 2]) float32.
+    Needs no device."""
+    d, rot = np.zeros((64, 3), np.float32), np.zeros((16, 2), np.float32)
+    rc = rt_lib().rt_ao_table(_ptr(d), _ptr(rot))
+    if rc != 0:
+        raise RTError("rt_ao_table", rc)
+    return d, rot
 
 
 _host_lib = None
@@ -884,6 +913,44 @@ class ComputeShader:
         fn.argtypes = [_P, _I, _I]
         fn.restype = _I
         self._chk(fn(self._h, int(walk), int(waves)), "rt_debug_gbuffer")
+
+    def ao(self, width, height, rays, radius, bias=1e-3, planes=AO_PLANES):
+        """rt_ao_host: ambient occlusion of the whole width x height frame as a dict of numpy
+        arrays: "count" [H, W] uint8, the occluded ones of each pixel's `rays` hemisphere rays
+        within `radius`, and "visibility" [H, W] float32 = (rays - count) / rays (1 on a miss)."""
+        out, g = {}, rt_ao()
+        for name in planes:
+            if name not in AO_PLANES:
+                raise ValueError(f"ao: unknown plane {name!r}")
+            a = np.empty((height, width), np.uint8 if name == "count" else np.float32)
+            out[name] = a
+            setattr(g, name, a.ctypes.data)
+            setattr(g, name + "_pitch", a.strides[0])
+        p = rt_ao_params(int(rays), float(radius), float(bias), 0)
+        self._chk(self._lib.rt_ao_host(self._h, int(width), int(height), C.byref(p), C.byref(g)), "rt_ao_host")
+        return out
+
+    def ao_device(self, width, height, y0, stripe, period, out_rows, rays, radius, bias=1e-3, count=None,
+                  visibility=None):
+        """rt_dispatch_ao: compact rows as dispatch_rows_ex; each plane a (device pointer, pitch
+        in bytes) pair or None. Stream-ordered, asynchronous."""
+        g = rt_ao()
+        for name, plane in (("count", count), ("visibility", visibility)):
+            if plane is not None:
+                setattr(g, name, plane[0])
+                setattr(g, name + "_pitch", plane[1])
+        p = rt_ao_params(int(rays), float(radius), float(bias), 0)
+        self._chk(self._lib.rt_dispatch_ao(self._h, int(width), int(height), int(y0), int(stripe), int(period),
+                                           int(out_rows), C.byref(p), C.byref(g)), "rt_dispatch_ao")
+
+    def debug_ao(self, form=0, waves=0):
+        """Diagnostics: the accelerated ambient-occlusion kernel walks its rays repacked over the
+        wave (form 1) or per hit lane (form 2; 0: the default form, per hit lane), with `waves` 8x8 tiles to a
+        block (0: default). Same planes either way."""
+        fn = self._lib.rt_debug_ao
+        fn.argtypes = [_P, _I, _I]
+        fn.restype = _I
+        self._chk(fn(self._h, int(form), int(waves)), "rt_debug_ao")
 
     def debug_ss_general(self, on):
         """Diagnostics: supersampled frames render the sample frame and filter it with a second
