@@ -639,6 +639,73 @@ int rt_ao_host(struct rt_ctx* ctx, int width, int height, const rt_ao_params* pa
  * device and no context. */
 int rt_ao_table(float* dirs64x3, float* rot16x2);
 
+/* Shaded rays: the frame's shading for rays the caller gives -- a second eye, the six faces of
+ * a probe, a fisheye or orthographic view, a lens, a sparse or foveated pattern, a mirror or
+ * portal view. A dispatch aims its rays with one pinhole camera (getRay,
+ * gpu_shader.comp:155-168); here the host aims them, and everything after the camera ray is the
+ * frame's: closest hit, Phong, the hard shadow, mirror bounces, Fresnel.
+ *
+ * Definition. Pixel i is the value main() of the reference shader (gpu_shader.comp:432-624)
+ * computes when its camera ray is ray i: acc = 0, att = 1, then up to maxBounces bounces; on a
+ * miss at any bounce the background mix((0.05, 0.07, 0.1), (0.5, 0.7, 1.0), sky) with that ray's
+ * own `sky` (a frame computes the same expression with sky = (float)y / resY); alpha exactly 1.
+ * The direction is used as given, without normalisation: in the walk, in reflect and as Phong's
+ * view vector (the shading assumes unit length; a direction of another length is shaded as the
+ * shader would shade it). A ray whose origin, direction and sky are bit-equal to what a dispatch
+ * generates for pixel (x, y) gets that pixel's bits, from every kernel variant.
+ *
+ * Formats. RT_FORMAT_RGBA32F (16 B per pixel, dev_pixels 16-byte aligned), RT_FORMAT_RGB32F
+ * (12 B, 4-byte aligned), RT_FORMAT_RGBA8 and RT_FORMAT_SRGBA8 (4 B, 4-byte aligned),
+ * RT_FORMAT_RGBA16F (8 B, 8-byte aligned), with the conversions rt_dispatch_rows_fmt defines.
+ * Pixels are compact: pixel i at i * bytes per pixel, and not one byte after pixel n - 1 is
+ * written. RT_FORMAT_RGBA32F_IMAGE and unknown formats are RT_ERR_INVALID.
+ *
+ * What applies: maxBounces, useBVH, useFresnel and useMollerTrumbore (the brute-force branch's
+ * 1e-5 shadow offset included), the light, rt_set_kernel and rt_set_tree. What does not enter:
+ * the camera, resX and resY, rt_set_samples, rt_set_adaptive, latency mode, schedule, tail and
+ * rt_set_walk. Rays are shaded in the order given, 64 consecutive rays to a wave: neighbours
+ * that point the same way are faster ("Your own camera"). The call never
+ * reorders rays.
+ *
+ * Like a query, the call first applies pending rt_update_shapes / rt_update_nodes / rt_animate
+ * work as one refit. It leaves alone the context surface, rt_accel_info::last_kernel, the record
+ * of rt_kernel_times / rt_last_kernel_ms, rt_sync_frame's marker, the tile cost order and
+ * rt_adaptive_stats. Overlapping ray and pixel buffers are undefined.
+ *
+ * Errors, returned before anything is launched. RT_ERR_INVALID: a NULL context, n < 0, a NULL
+ * pointer with n > 0, a bad format, a misaligned device pointer (rays 16 bytes, pixels as
+ * above). RT_ERR_NO_SCENE without a scene, a light or params; a camera is not needed. n == 0 is
+ * RT_OK and launches nothing. A scene without nodes gives every ray its background (with
+ * maxBounces > 0). */
+typedef struct rt_view_ray {   /* 32 bytes, 16-byte aligned */
+    float origin[3];
+    float sky;                 /* background parameter: the value a frame uses as y / resY */
+    float dir[3];              /* used as given; the shading assumes unit length */
+    int   reserved;            /* 0 */
+} rt_view_ray;
+
+RT_STATIC_ASSERT(sizeof(rt_view_ray) == 32 && offsetof(rt_view_ray, sky) == 12 && offsetof(rt_view_ray, dir) == 16 &&
+                 offsetof(rt_view_ray, reserved) == 28, "rt_view_ray");
+
+/* Device pointers; stream-ordered on the context's stream, asynchronous. */
+int rt_shade_rays(struct rt_ctx* ctx, const rt_view_ray* dev_rays, int n, void* dev_pixels, int format);
+
+/* Host pointers (any alignment), staged through buffers the context keeps between calls;
+ * returns when the pixels are in host memory. */
+int rt_shade_rays_host(struct rt_ctx* ctx, const rt_view_ray* rays, int n, void* pixels, int format);
+
+/* The generator a host starts from and perturbs: for y in [y0, y0 + rows) and x in [0, width),
+ * record (y - y0) * width + x holds the origin and direction a dispatch of a width x height
+ * frame generates for pixel (x, y), bit for bit (current camera, rt_params::resX / resY),
+ * sky = (float)y / resY (one IEEE division) and reserved = 0. So rt_shade_rays over the list is
+ * the frame's rows [y0, y0 + rows). RT_ERR_INVALID: width, height or rows <= 0, y0 < 0,
+ * y0 + rows > height (the list has no holes), a NULL pointer, a device pointer not 16-byte
+ * aligned, width * rows >= 2^31. RT_ERR_NO_SCENE without a camera or params; an uploaded scene
+ * is not needed. The device form is stream-ordered and asynchronous; the host form returns when
+ * the records are in host memory. */
+int rt_camera_rays(struct rt_ctx* ctx, int width, int height, int y0, int rows, rt_view_ray* dev_rays);
+int rt_camera_rays_host(struct rt_ctx* ctx, int width, int height, int y0, int rows, rt_view_ray* rays);
+
 /* Accelerator statistics for the uploaded scene. */
 int rt_accel_info_get(struct rt_ctx* ctx, rt_accel_info* out);
 

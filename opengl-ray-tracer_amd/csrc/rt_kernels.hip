@@ -39,6 +39,10 @@
 //       the caller's rays, or the camera rays of the caller's pixels, one per lane
 //       through lane_walk over the accelerator (k_trace) or through k_lane's literal
 //       walk (k_trace_ref); closest hit or occlusion within a limit per ray.
+//   k_shade<MT, SPLIT, DISP> / k_shade_ref<DISP> / k_camera_rays : shaded rays (rt_shade_rays,
+//       rt_camera_rays): the caller's rays through k_accel_tail's bounce loop from bounce 0,
+//       every walk per lane (k_shade), or through k_lane's literal loop (k_shade_ref), one
+//       compact pixel per ray; k_camera_rays writes a frame's own camera rays as such a list.
 //   k_gbuffer<MT, LANE> / k_gbuffer_ref : geometry buffers (rt_dispatch_gbuffer): the closest
 //       hit of every pixel's camera ray as planes of shape, depth, normal and position. One
 //       8x8 tile per wave through packet_walk (or lane_walk for a camera beyond the
@@ -225,6 +229,10 @@ __device__ __forceinline__ PixelCoord pixel_of(const KParams& kp) {
 // Background gradient (gpu_shader.comp:436).
 __device__ __forceinline__ V background(const KParams& kp, int y) {
     return mix(mk(0.05f, 0.07f, 0.1f), mk(0.5f, 0.7f, 1.0f), static_cast<float>(y) / kp.resY);
+}
+// The same gradient at a caller's parameter (rt_view_ray::sky; a frame's is y / resY).
+__device__ __forceinline__ V background(const KParams&, float sky) {
+    return mix(mk(0.05f, 0.07f, 0.1f), mk(0.5f, 0.7f, 1.0f), sky);
 }
 
 __device__ __forceinline__ Ray primary_ray(const KParams& kp, int x, int y) {
@@ -2137,6 +2145,105 @@ __global__ __launch_bounds__(kBlock) void k_trace_ref(TraceArgs q, KParams kp) {
 }
 
 // ---------------------------------------------------------------------------
+// Shaded rays (rt_shade_rays / rt_shade_rays_host / rt_camera_rays): the frame's bounce loop
+// for rays the caller gives, one ray per lane in the order given, one pixel per ray.
+
+struct ShadeArgs {
+    const float4* __restrict__ rays;  // rt_view_ray: origin | sky, dir | reserved
+    int n;
+};
+
+// Pixel i of the compact list as (row, column) of a surface 65,536 pixels wide (shade_launch
+// sets kp.pitch to match), so store_px's int column arithmetic holds for any n < 2^31.
+constexpr int kShadeRowShift = 16;
+__device__ __forceinline__ int shade_row(unsigned i) { return static_cast<int>(i >> kShadeRowShift); }
+__device__ __forceinline__ int shade_col(unsigned i) { return static_cast<int>(i & ((1u << kShadeRowShift) - 1u)); }
+
+// One wave per block over the accelerator, with k_trace's LDS stacks: k_accel_tail's loop around
+// bounce_step from depth 0, every walk a lane walk (lane_from = shadow_from = 0), so a ray's
+// origin and direction are its own (ray_consts decides per ray). The background parameter is
+// read again from the ray record on a miss, not kept live through the walks.
+template <bool MT, bool SPLIT, bool DISP>
+__global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_shade(AccelPtrs A, const float4* __restrict__ mat,
+                                                                 ShadeArgs q, KParams kp) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    unsigned short* stt =
+        reinterpret_cast<unsigned short*>(lds_stack + static_cast<size_t>(kp.lane_stack) * blockDim.x) + threadIdx.x;
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool alive = i < static_cast<unsigned>(q.n);
+    Ray ray{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 1.f)};
+    if (alive) {
+        const float4 a = q.rays[2 * static_cast<size_t>(i)], b = q.rays[2 * static_cast<size_t>(i) + 1];
+        ray = Ray{mk(a.x, a.y, a.z), mk(b.x, b.y, b.z)};
+    }
+    const bool have = alive;
+    V acc = mk(0.f, 0.f, 0.f), att = mk(1.f, 1.f, 1.f);
+    WalkCount wc{0u, 0u, 0u, 0u};
+    for (int depth = 0; depth < kp.maxBounces; ++depth) {
+        if (__ballot(alive) == 0) break;
+        bounce_step<false, false, MT, SPLIT>(A, mat, kp, depth, ray, alive, acc, att,
+                                             [&]() { return q.rays[2 * static_cast<size_t>(i)].w; }, stk, stt,
+                                             kp.lane_stack, wc, nullptr, 0, 0);
+    }
+    if (have)
+        store_px<DISP ? kStoreDisplay : kStoreFloat>(kp, shade_row(i), shade_col(i),
+                                                     make_float4(acc.x, acc.y, acc.z, 1.0f));
+}
+
+// The same pixels from k_lane's literal per-pixel loop (gpu_shader.comp:450-517), both useBVH
+// branches, with the ray and the background from the record (contexts without a usable
+// accelerator, RT_KERNEL_LANE / RT_KERNEL_PACKET): 256-thread blocks, k_lane's stacks.
+template <bool DISP>
+__global__ __launch_bounds__(kBlock) void k_shade_ref(ShadeArgs q, KParams kp) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= static_cast<unsigned>(q.n)) return;
+    const float4 ra = q.rays[2 * static_cast<size_t>(i)], rb = q.rays[2 * static_cast<size_t>(i) + 1];
+    const V bg = background(kp, ra.w);
+    Ray ray{mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z)};
+    V acc = mk(0.f, 0.f, 0.f), att = mk(1.f, 1.f, 1.f);
+    Counters c;
+    const float shadow_off = kp.useBVH ? 1e-3f : 1e-5f;  // :469 vs :565
+    for (int depth = 0; depth < kp.maxBounces; ++depth) {
+        const LaneHit hit = kp.useBVH ? lane_closest_bvh<false>(kp, kp.nodes, kp.geo_leaf, ray, stk, c)
+                                      : lane_closest_brute<false>(kp, kp.geo_lin, ray, c);
+        if (!hit.found) {
+            acc = acc + mulv(att, bg);
+            break;
+        }
+        const GeoRec g = load_rec(kp.useBVH ? kp.geo_leaf : kp.geo_lin, hit.slot);
+        const V hn = shape_normal(g, hit.p);
+        const Mat m = load_mat(kp.mat, g.idx);
+        const Ray sr{hit.p + hn * shadow_off, normalize(kp.light_pos - hit.p)};
+        const float ld = dist(kp.light_pos, hit.p);
+        bool shadow;
+        if (kp.useBVH) {
+            // Full closest-hit walk, as gpu_shader.comp:473-480.
+            const LaneHit sh = lane_closest_bvh<false>(kp, kp.nodes, kp.geo_leaf, sr, stk, c);
+            shadow = sh.found && sh.d < ld;
+        } else {
+            shadow = lane_shadow_brute<false>(kp, kp.geo_lin, sr, ld, c);
+        }
+        if (!shade_bounce(kp, ray, hit.p, hn, m, shadow, acc, att, 1e-3f)) break;
+    }
+    store_px<DISP ? kStoreDisplay : kStoreFloat>(kp, shade_row(i), shade_col(i), make_float4(acc.x, acc.y, acc.z, 1.0f));
+}
+
+// rt_camera_rays: record (y - y0) * width + x holds primary_ray of pixel (x, y) and the
+// background parameter a frame uses for row y; one thread per record.
+__global__ __launch_bounds__(kBlock) void k_camera_rays(KParams kp, float4* __restrict__ out, unsigned n) {
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const unsigned r = i / static_cast<unsigned>(kp.width);
+    const int x = static_cast<int>(i - r * static_cast<unsigned>(kp.width)), y = kp.y0 + static_cast<int>(r);
+    const Ray ray = primary_ray(kp, x, y);
+    out[2 * static_cast<size_t>(i)] = make_float4(ray.o.x, ray.o.y, ray.o.z, static_cast<float>(y) / kp.resY);
+    out[2 * static_cast<size_t>(i) + 1] = make_float4(ray.d.x, ray.d.y, ray.d.z, __int_as_float(0));
+}
+
+// ---------------------------------------------------------------------------
 // Geometry buffers (rt_dispatch_gbuffer / rt_gbuffer_host): the closest hit of every pixel's
 // camera ray as up to four planes (include/rt_api.h: shape, depth, normal, position).
 
@@ -3494,6 +3601,13 @@ struct rt_ctx {
     size_t ao_stage_cap = 0;
     int ao_form = 0;      // rt_debug_ao: 0 = the default form (per hit lane), 1 = repacked, 2 = per hit lane
     int ao_waves = 0;     // rt_debug_ao: waves (tiles) per block, 0 = the default
+    // rt_shade_rays_host / rt_camera_rays_host: staging for the rays and the pixels, grown on
+    // demand and kept between calls
+    float4* shade_in = nullptr;
+    size_t shade_in_cap = 0;
+    float4* shade_out = nullptr;
+    size_t shade_out_cap = 0;
+    int shade_split = 0;  // rt_debug_shade: 0 = the default k_shade instance, 1 = plain walks, 2 = split walks
     int kernel = RT_KERNEL_AUTO;
     int last_kind = 0;
     // own surface
@@ -5354,9 +5468,13 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
         // the root's bounds as kernel arguments while the host copy is current; once
         // rt_animate grew the boxes on the device, from the accelerator's copy of the
         // root record (which the refit keeps current)
+        // (not with maxBounces = 0: the shader traces nothing then and the pixel is black, while
+        // the kernel's root test would hand a ray that misses the root its background)
         k2.root_ok = 0;
-        if (kp.N > 0 && kp.useBVH && c->nodes_on_device_newer) k2.root_ok = 2;
-        if (kp.N > 0 && kp.useBVH && !c->nodes_on_device_newer && static_cast<int>(c->host_nodes.size()) == kp.N) {
+        const bool traces = kp.maxBounces > 0;
+        if (traces && kp.N > 0 && kp.useBVH && c->nodes_on_device_newer) k2.root_ok = 2;
+        if (traces && kp.N > 0 && kp.useBVH && !c->nodes_on_device_newer &&
+            static_cast<int>(c->host_nodes.size()) == kp.N) {
             const FlatNode& rn = c->host_nodes[kp.N - 1];
             k2.root_ok = 1;
             k2.root_lo[0] = rn.boundsMin.x;
@@ -5920,6 +6038,127 @@ int ao_launch(rt_ctx* c, int width, int height, int y0, int stripe, int period, 
     return RT_OK;
 }
 
+// Shaded rays. The checks of rt_shade_rays and rt_shade_rays_host (include/rt_api.h), before
+// anything is launched; RT_OK with *run = false when there is nothing to launch. `device`: the
+// pointers are device addresses and must be aligned for the kernels' loads and stores.
+int shade_check(const rt_ctx* c, const void* rays, int n, const void* pixels, int format, bool device, bool* run) {
+    *run = false;
+    if (!c || n < 0 || format == RT_FORMAT_RGBA32F_IMAGE || format_bytes(format) == 0 || (n > 0 && (!rays || !pixels)))
+        return RT_ERR_INVALID;
+    if (device && n > 0 &&
+        (reinterpret_cast<uintptr_t>(rays) % 16 != 0 || reinterpret_cast<uintptr_t>(pixels) % format_align(format) != 0))
+        return RT_ERR_INVALID;
+    if (!c->have_scene || !c->have_light || !c->have_params) return RT_ERR_NO_SCENE;
+    *run = n > 0;
+    return RT_OK;
+}
+
+// The k_shade instance with split walks (lane_walk_any's SPLIT) for barycentric scenes of at
+// least this many scene-tree items, the plain one below: k_accel's rule (RT_TAIL_AUTO).
+// Measured over the frame's own rays at 1920x1080, 3 bounces (tools/bench_shade.py,
+// profiles/shade_bench.jsonl), split against plain: the car (1,293 items) 0.376 against
+// 0.365 ms, +3 %; 100k triangles 4.514 against 4.555 ms, -1 %; the monkey scene +3 %.
+// Moller-Trumbore lists always take the plain instance, as every MT frame does.
+constexpr size_t kShadeSplitItems = kTailAutoItems;
+
+// One shading launch on the context's stream: pending scene writes first, as one refit; then
+// the context render_frame would take the frame to -- the brute sub-context for useBVH = 0
+// (shadow offset 1e-5), the Moller-Trumbore sub-context -- without accel_usable's camera test
+// (no camera enters; lane_walk handles any origin per ray); k_shade when that target's
+// accelerator is built for the wanted triangle test, else k_shade_ref over this context's own
+// records. Like a query it touches none of the render state.
+int shade_launch(rt_ctx* c, const float4* rays, int n, void* pixels, int format) {
+    if (const int rc = flush_updates(c)) return rc;
+    rt_ctx* t = c;
+    KParams sel;
+    std::memset(&sel, 0, sizeof sel);
+    sel.useBVH = c->params.useBVH;
+    sel.useMT = c->params.useMollerTrumbore;
+    float off = 1e-3f;
+    for (int hop = 0; hop < 2; ++hop) {
+        rt_ctx* nxt = brute_ctx(t, sel);
+        if (nxt) off = 1e-5f;  // gpu_shader.comp:565
+        else nxt = mt_ctx(t, sel);
+        if (!nxt) break;
+        sel.useBVH = nxt->params.useBVH;
+        sel.useMT = nxt->params.useMollerTrumbore;
+        t = nxt;
+    }
+    const bool mt = sel.useMT != 0;
+    const bool accel = (c->kernel == RT_KERNEL_AUTO || c->kernel == RT_KERNEL_ACCEL) && t->accel_ok && sel.useBVH &&
+                       t->accel.mt == mt;
+    if (!accel) t = c;
+    if (t != c) {  // the sub-context's own pending writes (launch() applies them for a frame)
+        if (const int rc = flush_updates(t)) return rc;
+    }
+    KParams kp;
+    std::memset(&kp, 0, sizeof kp);
+    kp.geo_leaf = t->geo_leaf;
+    kp.geo_lin = t->geo_lin;
+    kp.mat = t->mat;
+    kp.nodes = t->nodes;
+    kp.S = t->S;
+    kp.N = t->N;
+    kp.I = t->I;
+    kp.max_stack = t->max_stack < 1 ? 1 : t->max_stack;
+    kp.light_pos = V{c->light.position.x, c->light.position.y, c->light.position.z};
+    kp.light_color = V{c->light.color.x, c->light.color.y, c->light.color.z};
+    kp.maxBounces = c->params.maxBounces;
+    kp.useBVH = accel ? 1 : c->params.useBVH;
+    kp.useFresnel = c->params.useFresnel;
+    kp.useMT = accel ? (mt ? 1 : 0) : c->params.useMollerTrumbore;
+    kp.shadow_off = off;
+    kp.stripe = kp.period = 1;
+    kp.dst = static_cast<char*>(pixels);
+    kp.pitch = format_bytes(format) << kShadeRowShift;  // shade_row / shade_col
+    kp.rgb = format;
+    kp.ss = 1;
+    kp.heavy_parts = 1;
+    const ShadeArgs q{rays, n};
+    const bool disp = format >= RT_FORMAT_RGBA8;
+    if (accel) {
+        kp.lane_stack = t->lane_stack_override > 0 ? t->lane_stack_override : t->accel.max_stack;
+        const bool split = !mt && (c->shade_split ? c->shade_split == 2 : t->accel.st.item_ref.size() >= kShadeSplitItems);
+        auto kfn = mt      ? (disp ? k_shade<true, false, true> : k_shade<true, false, false>)
+                   : split ? (disp ? k_shade<false, true, true> : k_shade<false, true, false>)
+                           : (disp ? k_shade<false, false, true> : k_shade<false, false, false>);
+        const size_t lds = static_cast<size_t>(kp.lane_stack) * 64 * 6;
+        hipLaunchKernelGGL(kfn, dim3((static_cast<unsigned>(n) + 63u) / 64u), dim3(64), lds, c->stream, accel_ptrs(t),
+                           t->mat, q, kp);
+    } else {
+        auto kfn = disp ? k_shade_ref<true> : k_shade_ref<false>;
+        const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
+        hipLaunchKernelGGL(kfn, dim3((static_cast<unsigned>(n) + kBlock - 1u) / kBlock), dim3(kBlock), lds, c->stream, q,
+                           kp);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// The checks of rt_camera_rays and rt_camera_rays_host; no launch for an error.
+int camera_rays_check(const rt_ctx* c, int width, int height, int y0, int rows, const void* out, bool device) {
+    if (!c || width <= 0 || height <= 0 || rows <= 0 || y0 < 0 || static_cast<long long>(y0) + rows > height || !out ||
+        static_cast<long long>(width) * rows >= (1ll << 31) || (device && reinterpret_cast<uintptr_t>(out) % 16 != 0))
+        return RT_ERR_INVALID;
+    if (!c->have_cam || !c->have_params) return RT_ERR_NO_SCENE;
+    return RT_OK;
+}
+
+int camera_rays_launch(rt_ctx* c, int width, int height, int y0, int rows, float4* out) {
+    KParams kp;
+    std::memset(&kp, 0, sizeof kp);
+    fill_camera(c->cam, kp);
+    kp.resX = c->params.resX;
+    kp.resY = c->params.resY;
+    kp.width = width;
+    kp.height = height;
+    kp.y0 = y0;
+    const unsigned n = static_cast<unsigned>(width) * static_cast<unsigned>(rows);
+    hipLaunchKernelGGL(k_camera_rays, dim3((n + kBlock - 1u) / kBlock), dim3(kBlock), 0, c->stream, kp, out, n);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -6077,6 +6316,8 @@ int rt_destroy(rt_ctx* c) {
     hipFree(c->trace_hits);
     hipFree(c->gbuf_stage);
     hipFree(c->ao_stage);
+    hipFree(c->shade_in);
+    hipFree(c->shade_out);
     hipFree(c->tail_queue);
     hipFree(c->tail_counts);
     hipFree(c->tile_times);
@@ -6790,6 +7031,49 @@ int rt_ao_table(float* dirs64x3, float* rot16x2) {
     return RT_OK;
 }
 
+int rt_shade_rays(rt_ctx* c, const rt_view_ray* dev_rays, int n, void* dev_pixels, int format) {
+    bool run;
+    if (const int rc = shade_check(c, dev_rays, n, dev_pixels, format, true, &run)) return rc;
+    if (!run) return RT_OK;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    return shade_launch(c, reinterpret_cast<const float4*>(dev_rays), n, dev_pixels, format);
+}
+
+int rt_shade_rays_host(rt_ctx* c, const rt_view_ray* rays, int n, void* pixels, int format) {
+    bool run;
+    if (const int rc = shade_check(c, rays, n, pixels, format, false, &run)) return rc;
+    if (!run) return RT_OK;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    const size_t bytes = static_cast<size_t>(n) * format_bytes(format);
+    int rc = ensure_staging(c->shade_in, c->shade_in_cap, 2 * static_cast<size_t>(n));
+    if (rc == RT_OK) rc = ensure_staging(c->shade_out, c->shade_out_cap, (bytes + 15) / 16);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->shade_in, rays, static_cast<size_t>(n) * sizeof(rt_view_ray), hipMemcpyHostToDevice,
+                           c->stream));
+    if ((rc = shade_launch(c, c->shade_in, n, c->shade_out, format)) != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(pixels, c->shade_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(sync_stream(c));
+    return RT_OK;
+}
+
+int rt_camera_rays(rt_ctx* c, int width, int height, int y0, int rows, rt_view_ray* dev_rays) {
+    if (const int rc = camera_rays_check(c, width, height, y0, rows, dev_rays, true)) return rc;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    return camera_rays_launch(c, width, height, y0, rows, reinterpret_cast<float4*>(dev_rays));
+}
+
+int rt_camera_rays_host(rt_ctx* c, int width, int height, int y0, int rows, rt_view_ray* rays) {
+    if (const int rc = camera_rays_check(c, width, height, y0, rows, rays, false)) return rc;
+    if (set_dev(c) != RT_OK) return RT_ERR_DEVICE;
+    const size_t n = static_cast<size_t>(width) * static_cast<size_t>(rows);
+    // the rays' own staging buffer: a host may shade the list it just generated
+    if (const int rc = ensure_staging(c->shade_in, c->shade_in_cap, 2 * n)) return rc;
+    if (const int rc = camera_rays_launch(c, width, height, y0, rows, c->shade_in)) return rc;
+    HIP_TRY(hipMemcpyAsync(rays, c->shade_in, n * sizeof(rt_view_ray), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(sync_stream(c));
+    return RT_OK;
+}
+
 }  // extern "C"
 
 extern "C" int rt_accel_info_get(rt_ctx* c, rt_accel_info* out) {
@@ -7047,6 +7331,14 @@ extern "C" int rt_debug_ao(rt_ctx* c, int form, int waves) {
     if (!c || form < 0 || form > 2 || (waves != 0 && waves != 1 && waves != 2 && waves != 4)) return RT_ERR_INVALID;
     c->ao_form = form;
     c->ao_waves = waves;
+    return RT_OK;
+}
+
+// Diagnostics (tools/bench_shade.py): the barycentric k_shade instance with plain walks (1) or
+// with the split walks of sparse waves (2); 0 = the default choice. Same pixels either way.
+extern "C" int rt_debug_shade(rt_ctx* c, int split) {
+    if (!c || split < 0 || split > 2) return RT_ERR_INVALID;
+    c->shade_split = split;
     return RT_OK;
 }
 

@@ -85,6 +85,14 @@ HIT_DTYPE = np.dtype({
     "itemsize": 16,
 })
 
+# rt_view_ray (include/rt_api.h): the records of rt_shade_rays / rt_camera_rays
+VIEW_RAY_DTYPE = np.dtype({
+    "names": ["origin", "sky", "dir", "reserved"],
+    "formats": [("<f4", 3), "<f4", ("<f4", 3), "<i4"],
+    "offsets": [0, 12, 16, 28],
+    "itemsize": 32,
+})
+
 SPHERE, PLANE, WALL, TRIANGLE = 0, 1, 2, 3
 TRACE_CLOSEST, TRACE_ANY = 0, 1
 KERNEL_AUTO, KERNEL_LANE, KERNEL_PACKET, KERNEL_ACCEL = 0, 1, 2, 3
@@ -276,6 +284,10 @@ RT_SYMBOLS = {
     "rt_dispatch_ao": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "rt_ao_host": (_I, [_P, _I, _I, _P, _P]),
     "rt_ao_table": (_I, [_P, _P]),
+    "rt_shade_rays": (_I, [_P, _P, _I, _P, _I]),
+    "rt_shade_rays_host": (_I, [_P, _P, _I, _P, _I]),
+    "rt_camera_rays": (_I, [_P, _I, _I, _I, _I, _P]),
+    "rt_camera_rays_host": (_I, [_P, _I, _I, _I, _I, _P]),
     "rt_status_string": (C.c_char_p, [_I]),
 }
 
@@ -876,6 +888,68 @@ class ComputeShader:
         self._chk(self._lib.rt_trace_pixels(self._h, int(width), int(height), _ptr(xy), len(xy), _ptr(hits)),
                   "rt_trace_pixels")
         return hits["shape"].copy(), hits["distance"].copy(), hits["occluded"].copy()
+
+    @staticmethod
+    def make_view_rays(o, d, sky=None):
+        """VIEW_RAY_DTYPE records of n rays; sky (the background parameter, a frame's y / resY)
+        defaults to 0."""
+        o = np.asarray(o, np.float32).reshape(-1, 3)
+        rays = np.zeros(len(o), VIEW_RAY_DTYPE)
+        rays["origin"] = o
+        rays["dir"] = np.asarray(d, np.float32).reshape(-1, 3)
+        rays["sky"] = 0.0 if sky is None else np.asarray(sky, np.float32)
+        return rays
+
+    @staticmethod
+    def _pixel_array(n, fmt):
+        if fmt == FORMAT_RGB32F:
+            return np.empty((n, 3), np.float32)
+        if fmt not in SURFACE_DTYPE:
+            raise ValueError(f"shade_rays: no pixel list of format {fmt!r}")
+        return np.empty((n, 4), SURFACE_DTYPE[fmt])
+
+    def shade_rays(self, origins, dirs, sky=None, fmt=None):
+        """rt_shade_rays_host: the frame's shading (Phong, shadow, mirror bounces, Fresnel; the
+        background at each ray's own sky) for n caller rays, as an [n, 4] array of the format's
+        channel type ([n, 3] float32 for FORMAT_RGB32F). origins may also be a ready
+        VIEW_RAY_DTYPE array (dirs and sky None)."""
+        fmt = FORMAT_RGBA32F if fmt is None else fmt
+        if isinstance(origins, np.ndarray) and origins.dtype == VIEW_RAY_DTYPE and dirs is None:
+            rays = np.ascontiguousarray(origins).reshape(-1)
+        else:
+            rays = self.make_view_rays(origins, dirs, sky)
+        out = self._pixel_array(len(rays), fmt)
+        self._chk(self._lib.rt_shade_rays_host(self._h, _ptr(rays) if len(rays) else None, len(rays),
+                                               _ptr(out) if len(rays) else None, int(fmt)), "rt_shade_rays_host")
+        return out
+
+    def shade_rays_device(self, rays_ptr, n, dst_ptr, fmt=FORMAT_RGBA32F):
+        """rt_shade_rays: n VIEW_RAY_DTYPE records at device address rays_ptr (a torch tensor's
+        data_ptr()), compact pixels of format fmt to dst_ptr; stream-ordered, asynchronous."""
+        self._chk(self._lib.rt_shade_rays(self._h, C.c_void_p(rays_ptr) if rays_ptr else None, int(n),
+                                          C.c_void_p(dst_ptr) if dst_ptr else None, int(fmt)), "rt_shade_rays")
+
+    def camera_rays(self, width, height, y0=0, rows=None):
+        """rt_camera_rays_host: the camera rays a dispatch generates for rows [y0, y0 + rows) of a
+        width x height frame (current camera and params), as VIEW_RAY_DTYPE records, row-major."""
+        rows = height - y0 if rows is None else rows
+        rays = np.zeros(max(0, int(width)) * max(0, int(rows)), VIEW_RAY_DTYPE)
+        self._chk(self._lib.rt_camera_rays_host(self._h, int(width), int(height), int(y0), int(rows),
+                                                _ptr(rays) if len(rays) else None), "rt_camera_rays_host")
+        return rays
+
+    def camera_rays_device(self, width, height, y0, rows, rays_ptr):
+        """rt_camera_rays: the same records to device address rays_ptr; stream-ordered, asynchronous."""
+        self._chk(self._lib.rt_camera_rays(self._h, int(width), int(height), int(y0), int(rows),
+                                           C.c_void_p(rays_ptr) if rays_ptr else None), "rt_camera_rays")
+
+    def debug_shade(self, split=0):
+        """Diagnostics: the barycentric k_shade instance with plain walks (1) or with the split
+        walks of sparse waves (2); 0: the default choice. Same pixels either way."""
+        fn = self._lib.rt_debug_shade
+        fn.argtypes = [_P, _I]
+        fn.restype = _I
+        self._chk(fn(self._h, int(split)), "rt_debug_shade")
 
     def gbuffer(self, width, height, planes=GBUFFER_PLANES):
         """rt_gbuffer_host: the geometry buffer of the whole width x height frame as a dict of
