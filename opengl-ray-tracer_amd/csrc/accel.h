@@ -92,7 +92,7 @@ struct AccelHost {
     // of a ray origin the bounds are built for (kOriginRel * (scene_mag + 1)).
     // Rays from farther away take the always-enter mode of the padded tests
     // (accel_math.h); a camera farther away skips the accelerator for the
-    // frame (rt_kernels.hip, launch()).
+    // frame (rt_kernels.hip, accel_usable).
     float scene_mag = 0.f, origin_lim = 0.f;
     int always_prims = 0, bounded_prims = 0, local_leaves = 0;
     // Scene tree; its prims follow the local ones in prim_shape / prim_seq,

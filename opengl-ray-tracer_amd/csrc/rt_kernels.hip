@@ -23,7 +23,8 @@
 //       tile (or one band of a split heavy tile) per wave over the exact-result
 //       accelerator (accel.h): packet walks (packet_walk) for coherent rays,
 //       per-lane walks with LDS stacks (lane_walk) for the rest, same image as
-//       the kernels above. launch() picks the instance; the one without counters,
+//       the kernels above. rtp::accel_instance (dispatch_plan.h) picks the instance and
+//       accel_kernel() finds it; the one without counters,
 //       queue or records (k_accel<false, false>) renders the plain frames. The SS
 //       instances render supersampled frames (rt_set_samples): the sample frame's
 //       tiles, each n x n block of lanes stored as one mean pixel.
@@ -82,6 +83,7 @@
 #include "lbvh.h"
 #include "rt_device.h"
 #include "ao_table.h"
+#include "dispatch_plan.h"
 #include "group_wait.h"
 #include "rt_internal.h"
 
@@ -1643,7 +1645,6 @@ constexpr int kTileRec = 24;
 
 // Ray compaction (rt_set_tail): queue entries per 64x64-pixel region.
 constexpr int kTailRegion = 64 * 64;
-constexpr size_t kTailAutoItems = 8192;  // RT_TAIL_AUTO threshold
 
 // Cost-ordered dispatch (rt_set_schedule, k_tile_order): 32 half-octave
 // buckets of a tile's work; the render kernel counts them per group of
@@ -1654,11 +1655,7 @@ constexpr int kSplitMax = 16, kSplitGroup = 8;
 constexpr int kMtWalkFrom = 1 << 16;      // auto walk policy of Moller-Trumbore frames: all packets
 constexpr int kMtPacketMaxNodes = 1024;  // ... over reference trees of fewer nodes (walk_from)
 // the heaviest tiles of the cost order as several waves (rt_debug_heavy)
-constexpr int kHeavyTiles = -1, kHeavyParts = 4, kHeavyAutoSlots = 2;  // -1: auto
-// latency mode: frames of at most this many tiles per wave slot (16 per CU). 12: the car's
-// 3840x2160 half share (64,800 tiles) waited 0.360 ms with it against 0.318 without, its
-// quarter share (32,640) 0.19 against 0.27 (profiles/r05r_share_sweep.json)
-constexpr int kLatencyMaxSlots = 12;
+constexpr int kHeavyTiles = -1, kHeavyParts = 4;  // -1: auto (dispatch_plan.h, heavy_split)
 constexpr unsigned kXcds = 8;  // MI355X: 8 XCDs, workgroups dealt round-robin
 
 __device__ __forceinline__ int work_bucket(unsigned c) {
@@ -1842,7 +1839,7 @@ __device__ void accel_tile(const AccelPtrs& A, const float4* __restrict__ mat, c
 // SS: the supersampling instances (rt_set_samples): the same tiles over the sample frame,
 // each n x n block of lanes stored as one mean pixel (accel_tile).
 // DISP: the instance's twin for the display formats (RT_FORMAT_RGBA8, SRGBA8, RGBA16F: StoreKind
-// in rt_device.h); launch() takes it from kAccelTwins.
+// in rt_device.h); accel_kernel() takes it from kAccelTable.
 template <bool TIMED, bool COST = true, bool TAIL = false, bool MT = false, bool REC = COST, bool QUEUE = TAIL,
           bool SS = false, bool DISP = false>
 __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, const float4* __restrict__ mat, KParams kp) {
@@ -1938,7 +1935,7 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, con
     }
 }
 
-// Every k_accel instance launch() can choose, <TIMED, COST, TAIL, MT, REC, QUEUE, SS>, with
+// Every k_accel instance rtp::accel_instance (dispatch_plan.h) can choose, <TIMED, COST, TAIL, MT, REC, QUEUE, SS>, with
 // its twin for the display formats (DISP).
 #define RT_ACCEL_INSTANCES(X)                                                                    \
     X(false, false, false, false, false, false, false) X(false, false, false, false, false, false, true) \
@@ -1952,13 +1949,26 @@ __global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_accel(AccelPtrs A, con
     X(false, true, false, true, true, false, false) X(false, true, false, true, true, false, true)       \
     X(false, true, true, false, true, false, false) X(false, true, true, false, true, false, true)       \
     X(false, true, true, false, true, true, false) X(true, true, false, false, true, false, false)
-struct AccelTwin {
-    void (*plain)(AccelPtrs, const float4*, KParams);
-    void (*display)(AccelPtrs, const float4*, KParams);
+using AccelFn = void (*)(AccelPtrs, const float4*, KParams);
+struct AccelEntry {
+    rtp::AccelInstance args;
+    AccelFn plain, display;
 };
-#define RT_ACCEL_TWIN(...) {k_accel<__VA_ARGS__>, k_accel<__VA_ARGS__, true>},
-const AccelTwin kAccelTwins[] = {RT_ACCEL_INSTANCES(RT_ACCEL_TWIN)};
-#undef RT_ACCEL_TWIN
+#define RT_ACCEL_ENTRY(...) {{__VA_ARGS__}, k_accel<__VA_ARGS__>, k_accel<__VA_ARGS__, true>},
+const AccelEntry kAccelTable[] = {RT_ACCEL_INSTANCES(RT_ACCEL_ENTRY)};
+#undef RT_ACCEL_ENTRY
+
+// The instance rtp::accel_instance chose, or its twin compiled with the display formats'
+// conversion; nullptr for arguments without an entry (RT_ACCEL_INSTANCES is out of date).
+AccelFn accel_kernel(const rtp::AccelInstance& a, bool display) {
+    for (const AccelEntry& e : kAccelTable) {
+        const rtp::AccelInstance& b = e.args;
+        if (a.timed == b.timed && a.cost == b.cost && a.tail == b.tail && a.mt == b.mt && a.rec == b.rec &&
+            a.queue == b.queue && a.ss == b.ss)
+            return display ? e.display : e.plain;
+    }
+    return nullptr;
+}
 
 // The queued rays' remaining bounces (rt_set_tail): one wave per possible chunk
 // of 64 rays (kTailRegion / 64 per region), each taking one. The same bounce arithmetic as
@@ -3840,6 +3850,26 @@ int ensure_staging(T*& p, size_t& cap, size_t n) {
     return RT_OK;
 }
 
+// The dispatch path's device buffers (launch() and the steps under it): `p` of capacity `cap`
+// (in the caller's units) freed, and allocated again with `bytes` for capacity n. The caller
+// decides when (too small; ss_buf: any other size) and what precedes it (ss_buf, ad_list:
+// the stream's work). `zero`: zeroed on the context's stream before it counts as there;
+// otherwise the contents are undefined.
+template <class T, class C>
+void drop_buffer(T*& p, C& cap) {
+    hipFree(p);
+    p = nullptr;
+    cap = 0;
+}
+template <class T, class C>
+int renew_buffer(rt_ctx* c, T*& p, C& cap, C n, size_t bytes, bool zero = false) {
+    drop_buffer(p, cap);
+    if (hipMalloc(&p, bytes) != hipSuccess) return RT_ERR_NO_MEMORY;
+    if (zero) HIP_TRY(hipMemsetAsync(p, 0, bytes, c->stream));
+    cap = n;
+    return RT_OK;
+}
+
 void free_accel(rt_ctx* c) {
     hipFree(c->anodes);
     hipFree(c->lnodes);
@@ -4989,6 +5019,54 @@ void fill_camera(const FlatCamera& cam, KParams& kp) {
     kp.plane_w = h * cam.aspectRatio;
 }
 
+// The camera of `c` and its resolution, for the launches that form camera rays of the frame as set.
+void camera_params(const rt_ctx* c, KParams& kp) {
+    fill_camera(c->cam, kp);
+    kp.resX = c->params.resX;
+    kp.resY = c->params.resY;
+}
+
+// Per-lane LDS stack entries of the walks over t's accelerator (rt_debug_lane_stack overrides).
+int lane_stack_entries(const rt_ctx* t) {
+    return t->lane_stack_override > 0 ? t->lane_stack_override : t->accel.max_stack;
+}
+
+// The device scene of `t` and its stack depths: what every kernel's walks read.
+void scene_params(const rt_ctx* t, KParams& kp) {
+    kp.geo_leaf = t->geo_leaf;
+    kp.geo_lin = t->geo_lin;
+    kp.nodes = t->nodes;
+    kp.S = t->S;
+    kp.N = t->N;
+    kp.I = t->I;
+    kp.max_stack = t->max_stack < 1 ? 1 : t->max_stack;
+    kp.lane_stack = lane_stack_entries(t);
+}
+
+// Dynamic LDS: a wave's per-lane stacks over the accelerator (codes, then bf16 entry
+// parameters: 6 B an entry), and a block's stacks of the literal reference walk.
+size_t lane_stack_lds(const KParams& kp) { return static_cast<size_t>(kp.lane_stack) * 64 * 6; }
+size_t ref_stack_lds(const KParams& kp) { return static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int); }
+
+// The root's current bounds for the tile kernels' sky skip:
+// the root's bounds as kernel arguments while the host copy is current; once
+// rt_animate grew the boxes on the device, from the accelerator's copy of the
+// root record (which the refit keeps current)
+void root_bounds(const rt_ctx* t, KParams& kp) {
+    kp.root_ok = 0;
+    if (kp.N > 0 && t->nodes_on_device_newer) kp.root_ok = 2;
+    if (kp.N > 0 && !t->nodes_on_device_newer && static_cast<int>(t->host_nodes.size()) == kp.N) {
+        const FlatNode& rn = t->host_nodes[kp.N - 1];
+        kp.root_ok = 1;
+        kp.root_lo[0] = rn.boundsMin.x;
+        kp.root_lo[1] = rn.boundsMin.y;
+        kp.root_lo[2] = rn.boundsMin.z;
+        kp.root_hi[0] = rn.boundsMax.x;
+        kp.root_hi[1] = rn.boundsMax.y;
+        kp.root_hi[2] = rn.boundsMax.z;
+    }
+}
+
 // Bytes per pixel of an rt_format (0: not a format) and the alignment of its dst and pitch:
 // a pixel is one store of 16 B (RGBA32F), three of 4 B (RGB32F), one of 4 B (the 8-bit
 // formats) or one of 8 B (RGBA16F).
@@ -5019,14 +5097,8 @@ int fill_kparams(rt_ctx* c, int width, int height, int y0, int stripe, int perio
         (pitch % align) != 0 || (reinterpret_cast<uintptr_t>(dst) % align) != 0)
         return RT_ERR_INVALID;
     std::memset(&kp, 0, sizeof kp);
-    kp.geo_leaf = c->geo_leaf;
-    kp.geo_lin = c->geo_lin;
+    scene_params(c, kp);
     kp.mat = c->mat;
-    kp.nodes = c->nodes;
-    kp.S = c->S;
-    kp.N = c->N;
-    kp.I = c->I;
-    kp.max_stack = c->max_stack < 1 ? 1 : c->max_stack;
     fill_camera(c->cam, kp);
     kp.light_pos = V{c->light.position.x, c->light.position.y, c->light.position.z};
     kp.light_color = V{c->light.color.x, c->light.color.y, c->light.color.z};
@@ -5210,6 +5282,50 @@ int render(rt_ctx* c, const KParams& kp) {
     return rc;
 }
 
+// One hop of a frame or a ray list from `t` towards the context that renders it: the brute
+// sub-context (which sets the shader's shadow offset for useBVH = 0 in `off`), else the
+// Moller-Trumbore one, else nullptr. `sel`: the useBVH / useMT in force at `t`.
+rt_ctx* next_hop(rt_ctx* t, const KParams& sel, float& off) {
+    rt_ctx* nxt = brute_ctx(t, sel);
+    if (nxt) off = 1e-5f;  // gpu_shader.comp:565
+    else nxt = mt_ctx(t, sel);
+    return nxt;
+}
+
+// rt_set_kernel_timing: the event pair around one dispatch, from the ring while it has room
+// (rt_kernel_times), else the context's overflow pair (rt_last_kernel_ms alone).
+struct TimedSpan {
+    hipEvent_t e0, e1;
+    bool ended;  // e1 is recorded (mark_end)
+};
+
+int begin_timed(rt_ctx* c, TimedSpan& s) {
+    s = TimedSpan{c->ev0, c->ev1, false};
+    if (c->ring_used < static_cast<int>(c->ring0.size())) {
+        s.e0 = c->ring0[c->ring_used];
+        s.e1 = c->ring1[c->ring_used];
+    }
+    HIP_TRY(hipEventRecord(s.e0, c->stream));
+    return RT_OK;
+}
+
+// The span's end here on the stream, ahead of work end_timed's caller still issues.
+int mark_end(rt_ctx* c, TimedSpan& s) {
+    HIP_TRY(hipEventRecord(s.e1, c->stream));
+    s.ended = true;
+    return RT_OK;
+}
+
+int end_timed(rt_ctx* c, TimedSpan& s) {
+    if (!s.ended)
+        if (const int rc = mark_end(c, s)) return rc;
+    c->last0 = s.e0;
+    c->last1 = s.e1;
+    if (c->ring_used < static_cast<int>(c->ring0.size())) ++c->ring_used;
+    c->timed = true;
+    return RT_OK;
+}
+
 int render_frame(rt_ctx* c, const KParams& kp, rt_ctx** from) {
     // this context's own pending writes first, also when a sub-context renders the frame
     if (const int rc = flush_updates(c)) return rc;
@@ -5217,9 +5333,7 @@ int render_frame(rt_ctx* c, const KParams& kp, rt_ctx** from) {
     KParams kt = kp;
     for (int hop = 0; hop < 2; ++hop) {
         float off = kt.shadow_off;
-        rt_ctx* nxt = brute_ctx(t, kt);
-        if (nxt) off = 1e-5f;  // gpu_shader.comp:565
-        else nxt = mt_ctx(t, kt);
+        rt_ctx* nxt = next_hop(t, kt, off);
         if (!nxt) break;
         KParams kn;
         const int rc = fill_kparams(nxt, kt.width, kt.height, kt.y0, kt.stripe, kt.period, kt.out_rows,
@@ -5243,20 +5357,12 @@ int render_frame(rt_ctx* c, const KParams& kp, rt_ctx** from) {
         c->timed = false;  // no events recorded for this dispatch
         return rc;
     }
-    hipEvent_t e0 = c->ev0, e1 = c->ev1;
-    if (c->ring_used < static_cast<int>(c->ring0.size())) {
-        e0 = c->ring0[c->ring_used];
-        e1 = c->ring1[c->ring_used];
-    }
-    HIP_TRY(hipEventRecord(e0, c->stream));
+    TimedSpan span;
+    if (const int rc = begin_timed(c, span)) return rc;
     const int rc = launch(t, kt, false);
     if (rc != RT_OK) return rc;
     if (t->ad_ran) c->ad_from = t;
-    HIP_TRY(hipEventRecord(e1, c->stream));
-    c->last0 = e0;
-    c->last1 = e1;
-    if (c->ring_used < static_cast<int>(c->ring0.size())) ++c->ring_used;
-    c->timed = true;
+    if (const int rc2 = end_timed(c, span)) return rc2;
     c->last_kind = t->last_kind;
     t->ring_used = 0;  // its own records are not read
     return RT_OK;
@@ -5287,19 +5393,6 @@ void launch_box_filter(rt_ctx* c, const KParams& out) {
                        out.y0 / n, out.stripe / n, out.period / n, rows, out.rgb);
 }
 
-// The pixels a dispatch of the OUTPUT frame `k` writes: its compact rows below the frame's end.
-unsigned long long dispatch_pixels(const KParams& k) {
-    if (k.period == k.stripe)  // contiguous rows from y0
-        return static_cast<unsigned long long>(std::max(0, std::min(k.out_rows, k.height - k.y0))) * k.width;
-    unsigned long long rows = 0;
-    for (long long s = 0; s * k.stripe < k.out_rows; ++s) {
-        const long long base = k.y0 + s * k.period;
-        if (base >= k.height) break;
-        rows += std::min<long long>({k.stripe, k.out_rows - s * k.stripe, k.height - base});
-    }
-    return rows * static_cast<unsigned long long>(k.width);
-}
-
 // Passes 2 and 3 of rt_set_adaptive's fast path, behind the one-sample render of B into
 // c->ss_buf: `out` is B's frame with the dispatch's dst / pitch / format, `smp` the sample
 // frame. The host never reads the list's length: the refine grid is the worst case.
@@ -5312,9 +5405,222 @@ void launch_adaptive(rt_ctx* c, const AccelPtrs& A, const KParams& out, const KP
                            : (disp ? k_accel_refine<false, true> : k_accel_refine<false, false>);
     const unsigned long long per = 64 / (smp.ss * smp.ss);  // pixels per wave
     const unsigned long long px = static_cast<unsigned long long>(out.width) * out.out_rows;
-    const size_t lds = static_cast<size_t>(smp.lane_stack) * 64 * 6;
-    hipLaunchKernelGGL(kfn, dim3(static_cast<unsigned>((px + per - 1) / per)), dim3(64), lds, c->stream, A, c->mat,
-                       smp, c->ad_list, c->ad_count);
+    hipLaunchKernelGGL(kfn, dim3(static_cast<unsigned>((px + per - 1) / per)), dim3(64), lane_stack_lds(smp), c->stream,
+                       A, c->mat, smp, c->ad_list, c->ad_count);
+}
+
+// KParams' row mapping as dispatch_plan.h takes it, and back.
+rtp::Frame frame_of(const KParams& k) {
+    return rtp::Frame{k.width, k.height, k.y0, k.stripe, k.period, k.out_rows, k.resX, k.resY};
+}
+void set_frame(KParams& k, const rtp::Frame& f) {
+    k.width = f.width;
+    k.height = f.height;
+    k.y0 = f.y0;
+    k.stripe = f.stripe;
+    k.period = f.period;
+    k.out_rows = f.out_rows;
+    k.resX = f.resX;
+    k.resY = f.resY;
+}
+
+// The dispatch order of a k_accel frame of k2.tiles tiles, and whether it records its tiles'
+// costs for the next frame's (k2.tile_cost): the caller's own order (rt_set_tile_order), or
+// with rt_set_schedule the context's cost order once a frame of this size recorded one; a
+// cost frame when there is none, and every `period` frames.
+int cost_order_setup(rt_ctx* c, KParams& k2, int period) {
+    k2.tile_order = nullptr;
+    k2.tile_cost = nullptr;
+    if (c->tile_order && c->tile_order_n == k2.tiles) {
+        k2.tile_order = c->tile_order;
+        return RT_OK;
+    }
+    if (c->schedule == RT_SCHED_ROWS) return RT_OK;
+    if (c->sched_cap < k2.tiles) {
+        // costs, order and bucket sets share one capacity: the context's once all three stand
+        int cap = 0;
+        drop_buffer(c->sched_cost, c->sched_cap);
+        drop_buffer(c->sched_order, c->sched_cap);
+        drop_buffer(c->sched_sets, c->sched_cap);
+        c->sched_valid = 0;
+        if (renew_buffer(c, c->sched_cost, cap, k2.tiles, k2.tiles * sizeof(unsigned)) != RT_OK ||
+            renew_buffer(c, c->sched_order, cap, k2.tiles, k2.tiles * sizeof(int)) != RT_OK)
+            return RT_ERR_NO_MEMORY;
+        if (const int rc = renew_buffer(c, c->sched_sets, cap, k2.tiles,
+                                        2 * sched_set_words(k2.tiles) * sizeof(unsigned), true))
+            return rc;
+        c->sched_parity = 0;
+        c->sched_cap = cap;
+    }
+    k2.sched_hist = c->sched_sets + c->sched_parity * sched_set_words(c->sched_cap);
+    const bool have = c->sched_valid == k2.tiles;
+    if (have) k2.tile_order = c->sched_order;
+    if (!have || c->sched_frame % period == 0) {
+        k2.tile_cost = c->sched_cost;
+        c->sched_frame = 0;
+    }
+    ++c->sched_frame;
+    return RT_OK;
+}
+
+// The split tiles' part sums and counts of a cost frame (k_accel's comment), zeroed on the stream.
+int heavy_acc_setup(rt_ctx* c, KParams& k2) {
+    k2.heavy_acc = nullptr;
+    if (!k2.tile_cost || k2.heavy_k <= 0) return RT_OK;
+    const size_t need = static_cast<size_t>(k2.heavy_k);
+    if (c->heavy_acc_cap < need)
+        if (const int rc = renew_buffer(c, c->heavy_acc, c->heavy_acc_cap, need, need * sizeof(unsigned long long)))
+            return rc;
+    HIP_TRY(hipMemsetAsync(c->heavy_acc, 0, need * sizeof(unsigned long long), c->stream));
+    k2.heavy_acc = c->heavy_acc;
+    return RT_OK;
+}
+
+// The queue and the region counters of a compacting dispatch (rtp::tail_plan).
+int tail_setup(rt_ctx* c, KParams& k2, const rtp::TailPlan& t) {
+    const size_t need = static_cast<size_t>(t.regions) * kTailRegion;
+    if (need > c->tail_cap)
+        // 3 float4 records, then the pixel words (rt_device.h, tail_queue)
+        if (const int rc = renew_buffer(c, c->tail_queue, c->tail_cap, need, need * (3 * sizeof(float4) + sizeof(int))))
+            return rc;
+    if (t.regions > c->tail_regions_cap)
+        if (const int rc = renew_buffer(c, c->tail_counts, c->tail_regions_cap, t.regions,
+                                        2 * static_cast<size_t>(t.regions) * sizeof(int), true))
+            return rc;
+    k2.tail_queue = c->tail_queue;
+    k2.tail_px = reinterpret_cast<int*>(c->tail_queue + 3 * c->tail_cap);
+    k2.tail_count = c->tail_counts + c->tail_parity * c->tail_regions_cap;
+    k2.tail_count_next = c->tail_counts + (1 - c->tail_parity) * c->tail_regions_cap;
+    k2.tail_from = t.tail_from;
+    k2.tail_rx = t.rx;
+    k2.tail_regions = t.regions;
+    k2.tail_counters = c->tail_regions_cap;
+    k2.tail_max_lanes = c->tail_max_lanes;
+    return RT_OK;
+}
+
+// Behind a cost frame's render:
+// the next frame's order; stream-ordered after this dispatch (and after its
+// end event, so rt_kernel_times is the render kernel alone), before the next
+int launch_cost_order(rt_ctx* c, const KParams& k2, bool latency, int dilate, TimedSpan* span) {
+    if (span)
+        if (const int rc = mark_end(c, *span)) return rc;
+    const unsigned* set = c->sched_sets + c->sched_parity * sched_set_words(c->sched_cap);
+    unsigned* next = c->sched_sets + (1 - c->sched_parity) * sched_set_words(c->sched_cap);
+    const int groups = (k2.tiles + kOrderThreads - 1) / kOrderThreads;
+    const unsigned* cost = c->sched_cost;
+    if (latency && c->frame_event) {
+        // a waited frame ends here (rt_sync_frame); the order runs behind it on the same
+        // stream, within the host's turnaround to the next dispatch
+        if (!c->frame_ev && hipEventCreateWithFlags(&c->frame_ev, hipEventDisableTiming) != hipSuccess)
+            return RT_ERR_DEVICE;
+        HIP_TRY(hipEventRecord(c->frame_ev, c->stream));
+        c->frame_ev_set = true;
+    }
+    if (dilate > 0) {
+        const size_t need = static_cast<size_t>(k2.tiles) + static_cast<size_t>(groups) * kOrderBuckets;
+        if (c->dil_cap < need)
+            if (const int rc = renew_buffer(c, c->dil_cost, c->dil_cap, need, need * sizeof(unsigned))) return rc;
+        hipLaunchKernelGGL(k_cost_dilate, dim3(groups), dim3(kOrderThreads), 0, c->stream, c->sched_cost,
+                           k2.tiles, k2.tiles_x, dilate, c->dil_cost, c->dil_cost + k2.tiles);
+        cost = c->dil_cost;
+        set = c->dil_cost + k2.tiles;
+    }
+    hipLaunchKernelGGL(k_tile_order, dim3(groups), dim3(kOrderThreads),
+                       0, c->stream, cost, k2.tiles, set, next,
+                       static_cast<int>(sched_set_words(c->sched_cap)), c->sched_order,
+                       c->schedule == RT_SCHED_COST_XCD ? 1 : 0);
+    c->sched_parity = 1 - c->sched_parity;
+    c->sched_valid = k2.tiles;
+    return RT_OK;
+}
+
+// launch()'s RT_KERNEL_ACCEL branch. `kp`: the frame k_accel renders; `kin`: the dispatch's
+// own frame, `kout` its one-sample output frame (rt_set_adaptive); `span`: the dispatch's
+// timing span, or nullptr when it records none.
+int launch_accel(rt_ctx* c, const KParams& kin, const KParams& kout, const KParams& kp, const rtp::Samples& sp,
+                 TimedSpan* span) {
+    KParams k2 = kp;
+    k2.tiles_x = (kp.width + 7) / 8;
+    k2.tiles = k2.tiles_x * ((kp.out_rows + 7) / 8);
+    const bool latency = rtp::latency_frame(c->latency_mode, k2.tiles, c->cu_count);
+    // a moved camera's cost order (moving_period): waited frames only -- with frames in
+    // flight a cost frame after every move cost the car's orbit 0.194 -> 0.238 ms per
+    // frame (r05j), and the order matters less there
+    c->moving = latency && c->have_sched_cam && std::memcmp(&c->sched_cam, &c->cam, sizeof c->cam) != 0 &&
+                c->moving_period > 0;
+    c->sched_cam = c->cam;
+    c->have_sched_cam = true;
+    const int period = c->moving ? c->moving_period : c->sched_period;
+    const int dilate = c->moving ? c->moving_dilate : c->cost_dilate;
+    k2.tile_times = c->tile_times;
+    if (c->tile_times)
+        HIP_TRY(hipMemsetAsync(c->tile_times, 0, kTileRec * c->tile_times_cap * sizeof(unsigned long long),
+                               c->stream));
+    k2.heavy_k = 0;
+    k2.heavy_parts = 1;
+    if (const int rc = cost_order_setup(c, k2, period)) return rc;
+    k2.lane_from_depth = walk_from(c);
+    // (not with maxBounces = 0: the shader traces nothing then and the pixel is black, while
+    // the kernel's root test would hand a ray that misses the root its background)
+    k2.root_ok = 0;
+    if (kp.maxBounces > 0 && kp.useBVH) root_bounds(c, k2);
+    // big scenes (the RT_TAIL_AUTO criterion): camera rays' shadow walks per lane too
+    // (measured on config 5: -3.7 %; on the car the packet walk is faster)
+    const size_t items = c->accel.st.item_ref.size();
+    k2.shadow_lane_from = c->shadow_walk_override >= 0 ? c->shadow_walk_override
+                          : (rtp::many_items(items) && k2.lane_from_depth <= 1 ? 0 : k2.lane_from_depth);
+    k2.lane_stack = lane_stack_entries(c);  // the accelerator's as flush_updates left it
+    const bool lanes = std::min(k2.lane_from_depth, k2.shadow_lane_from) < k2.maxBounces;
+    const bool ordered = k2.tile_order && k2.tile_order == c->sched_order;
+    if (ordered) {
+        const rtp::LaneSlots ls = rtp::lane_k_slots(c->lane_k, c->lane_k_mode, lanes, k2.tiles);
+        if (ls.k > 0) {
+            k2.lane_k = ls.k;
+            k2.lane_k_mode = ls.mode;
+        }
+    }
+    // LDS stacks for the per-lane walks (also those of the lane_k slots)
+    const size_t lds = lanes || k2.lane_k > 0 ? lane_stack_lds(k2) : 0;
+    if (ordered) {
+        const bool whole = k2.tile_cost && c->cost_time != 0 && !c->tile_times && latency &&
+                           !(c->moving && c->moving_split);
+        const rtp::HeavySplit hs = rtp::heavy_split(rtp::HeavyIn{
+            k2.tiles, c->cu_count, latency, lanes, c->heavy_k, c->heavy_parts, c->tile_times != nullptr,
+            c->tile_times_cap, whole, sp.ss_fused, k2.ss});
+        k2.heavy_k = hs.k;
+        k2.heavy_parts = hs.parts;
+    }
+    // the cost measure: explicit (rt_debug_cost_time) or the waves' wall time
+    k2.cost_time = c->cost_time != 0 ? 1 : 0;
+    if (const int rc = heavy_acc_setup(c, k2)) return rc;
+    const AccelPtrs A = accel_ptrs(c);
+    k2.tail_queue = nullptr;
+    const rtp::TailPlan tp = rtp::tail_plan(c->tail_from, items, k2.maxBounces, sp.ss_fused, k2.width, k2.out_rows,
+                                            k2.tiles_x, k2.tiles);
+    if (tp.tail)
+        if (const int rc = tail_setup(c, k2, tp)) return rc;
+    const rtp::Cost cost = !k2.tile_cost ? rtp::kCostNone : k2.cost_time ? rtp::kCostTime : rtp::kCostCounters;
+    const rtp::AccelInstance inst =
+        rtp::accel_instance(c->accel.mt, c->tile_times != nullptr, tp.tail, latency, cost, sp.ss_fused);
+    if (!inst.queue) k2.tail_queue = nullptr;  // an instance without compaction
+    const AccelFn kfn = accel_kernel(inst, k2.rgb >= RT_FORMAT_RGBA8);
+    if (!kfn) return RT_ERR_INVALID;
+    // one wave per dispatch slot: the split heavy tiles' extra waves too
+    const int blocks = k2.tiles + k2.heavy_k * (k2.heavy_parts - 1);
+    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(64), lds, c->stream, A, c->mat, k2);
+    if (inst.queue) {
+        const int tgrid = tp.regions * (kTailRegion / 64);  // one wave per possible chunk
+        hipLaunchKernelGGL(k_accel_tail, dim3(tgrid), dim3(64), lane_stack_lds(k2), c->stream, A, c->mat, k2);
+        c->tail_parity = 1 - c->tail_parity;
+    }
+    if (sp.filter) launch_box_filter(c, kin);
+    if (sp.ad_fast) {
+        KParams smp = kin;  // the sample frame, walked per lane
+        smp.lane_stack = k2.lane_stack;
+        launch_adaptive(c, A, kout, smp);
+    }
+    return k2.tile_cost ? launch_cost_order(c, k2, latency, dilate, span) : RT_OK;
 }
 
 int launch(rt_ctx* c, const KParams& kin, bool stats) {
@@ -5328,442 +5634,66 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
     const bool usable = accel_usable(c, kin);
     if (kind == RT_KERNEL_AUTO) kind = usable ? RT_KERNEL_ACCEL : RT_KERNEL_PACKET;
     if (kind == RT_KERNEL_ACCEL && !usable) kind = RT_KERNEL_PACKET;  // same image either way
-    // rt_set_samples: k_accel reduces the samples in its store (the SS instances, fused);
-    // every other frame -- the lane and packet kernels, per-tile records (their instance has
-    // no SS form), rt_debug_ss_general -- is the one-sample render of the sample frame into
-    // the context's scratch surface, then k_box_filter (general).
-    const bool ss = !stats && kin.ss > 1;
-    const bool ss_accel = ss && kind == RT_KERNEL_ACCEL && !c->tile_times && !c->ss_general;
-    // rt_set_adaptive: where k_accel would reduce the samples (fast path), it renders the
-    // one-sample frame B into the scratch surface instead -- this dispatch from here on, with
-    // every setting of a one-sample frame -- and launch_adaptive refines the contrast pixels;
-    // every other frame keeps the general path with the adaptive filter kernel.
-    const bool adaptive = ss && c->adaptive >= 0.0f;
-    const bool ad_fast = adaptive && ss_accel;
-    const bool ss_fused = ss_accel && !ad_fast;
-    // rt_debug_convert_pass: a one-sample display frame the same way, float frame first, then
-    // the filter kernel's conversion (the measurement's baseline, tools/bench_formats.py)
-    const bool filter = ss ? !ss_accel : !stats && c->convert_pass && kin.rgb >= RT_FORMAT_RGBA8;
+    const rtp::Samples sp =
+        rtp::samples_plan(stats, kin.ss, kind == RT_KERNEL_ACCEL, c->tile_times != nullptr, c->ss_general,
+                          c->adaptive >= 0.0f, c->convert_pass, kin.rgb >= RT_FORMAT_RGBA8);
     KParams kout = kin;  // adaptive: the one-sample output frame, B's, with the dispatch's dst / pitch / format
-    if (adaptive) {      // (the dispatch scaled it by n: every value is a multiple, the floats exact)
-        const int n = kin.ss;
-        kout.width = kin.width / n;
-        kout.height = kin.height / n;
-        kout.y0 = kin.y0 / n;
-        kout.stripe = kin.stripe / n;
-        kout.period = kin.period / n;
-        kout.out_rows = kin.out_rows / n;
-        kout.resX = kin.resX / static_cast<float>(n);
-        kout.resY = kin.resY / static_cast<float>(n);
+    if (sp.adaptive) {
+        set_frame(kout, rtp::output_frame(frame_of(kin), kin.ss));
         kout.ss = 1;
     }
-    KParams kp = ad_fast ? kout : kin;
-    if (adaptive) {
+    KParams kp = sp.ad_fast ? kout : kin;
+    if (sp.adaptive) {
         if (!c->ad_count && hipMalloc(&c->ad_count, 4 * sizeof(unsigned)) != hipSuccess) return RT_ERR_NO_MEMORY;
         const size_t cap = static_cast<size_t>(kout.width) * static_cast<size_t>(kout.out_rows);
-        if (ad_fast && cap > c->ad_cap) {
+        if (sp.ad_fast && cap > c->ad_cap) {
             HIP_TRY(sync_stream(c));
-            hipFree(c->ad_list);
-            c->ad_list = nullptr;
-            c->ad_cap = 0;
-            if (hipMalloc(&c->ad_list, cap * sizeof(unsigned)) != hipSuccess) return RT_ERR_NO_MEMORY;
-            c->ad_cap = cap;
+            if (const int rc = renew_buffer(c, c->ad_list, c->ad_cap, cap, cap * sizeof(unsigned))) return rc;
         }
     }
-    if (filter || ad_fast) {
+    if (sp.filter || sp.ad_fast) {
         const size_t spitch = static_cast<size_t>(kp.width) * sizeof(float4);
         const size_t need = spitch * static_cast<size_t>(kp.out_rows);
         if (need != c->ss_bytes) {
             HIP_TRY(sync_stream(c));
-            hipFree(c->ss_buf);
-            c->ss_buf = nullptr;
-            c->ss_bytes = 0;
-            if (hipMalloc(&c->ss_buf, need) != hipSuccess) return RT_ERR_NO_MEMORY;
-            c->ss_bytes = need;
+            if (const int rc = renew_buffer(c, c->ss_buf, c->ss_bytes, need, need)) return rc;
         }
         kp.dst = c->ss_buf;
         kp.pitch = spitch;
         kp.rgb = RT_FORMAT_RGBA32F;
         kp.ss = 1;
     }
-    const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
+    const size_t lds = ref_stack_lds(kp);
     const bool rec = !stats && c->timing;  // rt_set_kernel_timing
-    hipEvent_t e0 = c->ev0, e1 = c->ev1;
-    if (rec && c->ring_used < static_cast<int>(c->ring0.size())) {
-        e0 = c->ring0[c->ring_used];
-        e1 = c->ring1[c->ring_used];
-    }
-    if (rec) HIP_TRY(hipEventRecord(e0, c->stream));
-    if (adaptive) {
+    TimedSpan span;
+    if (rec)
+        if (const int rc = begin_timed(c, span)) return rc;
+    if (sp.adaptive) {
         // the refined-pixel counter, zeroed in stream order; its last value stays for rt_adaptive_stats
         HIP_TRY(hipMemsetAsync(c->ad_count, 0, sizeof(unsigned), c->stream));
         c->ad_ran = true;
         c->ad_from = c;
-        c->ad_pixels = dispatch_pixels(kout);
+        c->ad_pixels = rtp::dispatch_pixels(frame_of(kout));
     }
-    bool order_after = false;  // e1 already recorded between the render and the order kernel
     if (stats) {
         hipLaunchKernelGGL(k_lane<true>, grid, dim3(kBlock), lds, c->stream, c->geo_leaf, c->geo_lin, c->mat,
                            c->nodes, kp);
     } else if (kind == RT_KERNEL_LANE) {
         hipLaunchKernelGGL(k_lane<false>, grid, dim3(kBlock), lds, c->stream, c->geo_leaf, c->geo_lin, c->mat,
                            c->nodes, kp);
-        if (filter) launch_box_filter(c, kin);
+        if (sp.filter) launch_box_filter(c, kin);
     } else if (kind == RT_KERNEL_ACCEL) {
-        KParams k2 = kp;
-        k2.tiles_x = (kp.width + 7) / 8;
-        k2.tiles = k2.tiles_x * ((kp.out_rows + 7) / 8);
-        // rt_set_latency_mode applies to frames of at most kLatencyMaxSlots tiles per wave
-        // slot: a bigger frame keeps the chip busy on its own, and the split-walk instance's
-        // throughput cost then outweighs the shorter chains (waited frame, latency mode on
-        // against off: car 1080p 0.216 against 0.262 ms; car 3840x2160 0.706 against 0.626;
-        // config 5 3.364 against 3.332; profiles/r04zz2_latency_sweep_*.json)
-        const bool latency = c->latency_mode && k2.tiles <= kLatencyMaxSlots * c->cu_count * 16;
-        // a moved camera's cost order (moving_period): waited frames only -- with frames in
-        // flight a cost frame after every move cost the car's orbit 0.194 -> 0.238 ms per
-        // frame (r05j), and the order matters less there
-        c->moving = latency && c->have_sched_cam && std::memcmp(&c->sched_cam, &c->cam, sizeof c->cam) != 0 &&
-                    c->moving_period > 0;
-        c->sched_cam = c->cam;
-        c->have_sched_cam = true;
-        const int period = c->moving ? c->moving_period : c->sched_period;
-        const int dilate = c->moving ? c->moving_dilate : c->cost_dilate;
-        k2.tile_times = c->tile_times;
-        if (c->tile_times)
-            HIP_TRY(hipMemsetAsync(c->tile_times, 0, kTileRec * c->tile_times_cap * sizeof(unsigned long long),
-                                   c->stream));
-        k2.tile_order = nullptr;
-        k2.tile_cost = nullptr;
-        k2.heavy_k = 0;
-        k2.heavy_parts = 1;
-        if (c->tile_order && c->tile_order_n == k2.tiles) {
-            k2.tile_order = c->tile_order;
-        } else if (c->schedule != RT_SCHED_ROWS) {
-            if (c->sched_cap < k2.tiles) {
-                hipFree(c->sched_cost);
-                hipFree(c->sched_order);
-                hipFree(c->sched_sets);
-                c->sched_cost = nullptr;
-                c->sched_order = nullptr;
-                c->sched_sets = nullptr;
-                c->sched_cap = c->sched_valid = 0;
-                if (hipMalloc(&c->sched_cost, k2.tiles * sizeof(unsigned)) != hipSuccess ||
-                    hipMalloc(&c->sched_order, k2.tiles * sizeof(int)) != hipSuccess ||
-                    hipMalloc(&c->sched_sets, 2 * sched_set_words(k2.tiles) * sizeof(unsigned)) != hipSuccess)
-                    return RT_ERR_NO_MEMORY;
-                HIP_TRY(hipMemsetAsync(c->sched_sets, 0, 2 * sched_set_words(k2.tiles) * sizeof(unsigned), c->stream));
-                c->sched_parity = 0;
-                c->sched_cap = k2.tiles;
-            }
-            k2.sched_hist = c->sched_sets + c->sched_parity * sched_set_words(c->sched_cap);
-            const bool have = c->sched_valid == k2.tiles;
-            if (have) k2.tile_order = c->sched_order;
-            if (!have || c->sched_frame % period == 0) {
-                k2.tile_cost = c->sched_cost;
-                c->sched_frame = 0;
-            }
-            ++c->sched_frame;
-        }
-        k2.lane_from_depth = walk_from(c);
-        // the root's bounds as kernel arguments while the host copy is current; once
-        // rt_animate grew the boxes on the device, from the accelerator's copy of the
-        // root record (which the refit keeps current)
-        // (not with maxBounces = 0: the shader traces nothing then and the pixel is black, while
-        // the kernel's root test would hand a ray that misses the root its background)
-        k2.root_ok = 0;
-        const bool traces = kp.maxBounces > 0;
-        if (traces && kp.N > 0 && kp.useBVH && c->nodes_on_device_newer) k2.root_ok = 2;
-        if (traces && kp.N > 0 && kp.useBVH && !c->nodes_on_device_newer &&
-            static_cast<int>(c->host_nodes.size()) == kp.N) {
-            const FlatNode& rn = c->host_nodes[kp.N - 1];
-            k2.root_ok = 1;
-            k2.root_lo[0] = rn.boundsMin.x;
-            k2.root_lo[1] = rn.boundsMin.y;
-            k2.root_lo[2] = rn.boundsMin.z;
-            k2.root_hi[0] = rn.boundsMax.x;
-            k2.root_hi[1] = rn.boundsMax.y;
-            k2.root_hi[2] = rn.boundsMax.z;
-        }
-        // big scenes (the RT_TAIL_AUTO criterion): camera rays' shadow walks per lane too
-        // (measured on config 5: -3.7 %; on the car the packet walk is faster)
-        const bool big = c->accel.st.item_ref.size() >= kTailAutoItems;
-        k2.shadow_lane_from = c->shadow_walk_override >= 0 ? c->shadow_walk_override
-                              : (big && k2.lane_from_depth <= 1 ? 0 : k2.lane_from_depth);
-        k2.lane_stack = c->lane_stack_override > 0 ? c->lane_stack_override : c->accel.max_stack;
-        if (k2.tile_order && k2.tile_order == c->sched_order) {
-            // the first lane_k dispatch slots (the heaviest tiles): explicit (rt_debug_lane_k)
-            // or auto -- in frames that walk per lane anyway (LDS stacks allocated), the
-            // heaviest 1/128 of the tiles walk their camera rays' shadows per lane: shorter
-            // chains on the slowest tiles (car: serial -5.5 %, 2 in flight equal, r02q)
-            int lk = c->lane_k, lm = c->lane_k_mode;
-            if (lk < 0) {
-                const bool lanes = std::min(k2.lane_from_depth, k2.shadow_lane_from) < k2.maxBounces;
-                lk = lanes ? std::max(64, k2.tiles / 128) : 0;
-                lm = 2;
-            }
-            if (lk > 0 && lm > 0) {
-                k2.lane_k = lk;
-                k2.lane_k_mode = lm;
-            }
-        }
-        // LDS stacks for the per-lane walks (also those of the lane_k slots)
-        const size_t lds = std::min(k2.lane_from_depth, k2.shadow_lane_from) < k2.maxBounces || k2.lane_k > 0
-                               ? static_cast<size_t>(k2.lane_stack) * 64 * 6
-                               : 0;
-        if (k2.tile_order && k2.tile_order == c->sched_order) {
-            // heavy tiles: explicit (rt_debug_heavy) or auto. A frame of at most
-            // kHeavyAutoSlots waves per wave slot whose walks are all packets (config 2:
-            // 800x600, primary + shadow) is bound by its slowest tiles even with frames
-            // in flight, and a packet walks the union of its rays' nodes: the heaviest
-            // 1/256 of its tiles run as 8 waves of 8 rays (measured -20 %, r02n). Where
-            // per-lane walks dominate the slow tiles (the car's reflections) it loses.
-            int hk = c->heavy_k, hp = c->heavy_parts;
-            if (hk < 0) {
-                const bool small = k2.tiles <= kHeavyAutoSlots * c->cu_count * 16 &&
-                                   std::min(k2.lane_from_depth, k2.shadow_lane_from) >= k2.maxBounces;
-                hk = small ? std::max(16, k2.tiles / 256) : 0;
-                hp = small ? 8 : 1;
-                if (small && latency) {
-                    // Waited, such a frame ends on its heaviest packet chains: split into 32
-                    // waves of 2 rays, a tile's parts walk little more than their own rays'
-                    // nodes. Config 2 waited (Python loop, tools/latency_sweep.py, r06k-r06m):
-                    // 29 x 8 (the in-flight rule) 0.0957 ms, 40 x 16 0.0907, 40 x 32 0.0793,
-                    // 60 / 120 x 32 0.0798, 20 x 32 0.0819, 40 x 64 0.0855. In flight the
-                    // in-flight rule stays best (4 frames: 0.0314 against 0.0416 with 40 x 32).
-                    hk = std::max(16, k2.tiles / 128);
-                    hp = 32;
-                }
-                if (!small && latency) {
-                    // rt_set_latency_mode: the heaviest 1/200 as 4 waves. Car waited frame with the
-                    // wall-time cost order and whole-tile cost frames (Python loop,
-                    // profiles/r04z7_latency_sweep.json, r04z8_latency_sweep.json), heaviest k as
-                    // 4 waves: k = 95 0.2362 ms, 126 0.2161, 159 0.2184, 191 0.2203, 255 0.2260;
-                    // as 2 waves: 63 0.2371, 127-511 0.224, 1023 0.229; 126 as 8: 0.2275. Some
-                    // tiles ranked ~96-126 by whole time gain most from the split, so k sits
-                    // well above that edge (162 of the car's 32,400 tiles).
-                    // A frame of few tiles per CU (a rank's stripe share of a strong frame) has
-                    // idle CUs to spread its heaviest chains over: the car's 1/8 share (4,080
-                    // tiles, 16 per CU) waited 0.175 ms by the whole-frame rule, 0.135-0.144 with
-                    // its heaviest 1/25 as 16 waves; the 1/4 share (8,160) 0.175-0.192 against
-                    // 0.156-0.160 with 1/25-1/50 as 8 waves; the 1/2 share mixed (C++ host loop,
-                    // tools/share_sweep.py, profiles/r05s/r05t_share_sweep*.json)
-                    // Off the tuned view the 4-wave split lost: four still cameras along
-                    // bench.py's orbit waited 0.213 / 0.279 / 0.277 / 0.294 ms with it, 0.216 /
-                    // 0.268 / 0.268 / 0.284 as 2 waves (geometric mean over the views 1.034
-                    // against 1.011 of each view's best of a 4 x 3 grid; tools/view_sweep.py,
-                    // profiles/r05za_view_sweep.json): whole frames that walk rays per lane take
-                    // 2 waves. All-packet frames (the MT car) keep 4: 2.68 ms with 2 against 1.75
-                    // (r05zl); the heaviest 1/400 as 8, best over two orbit views (geometric mean
-                    // 1.782 against 1.864 ms, r05zn_view_sweep_mt.json), measured 1.770 against
-                    // 1.755 at the bench's view and 1.933 against 1.844 animated (r05zo): kept 4
-                    const int per_cu = k2.tiles / std::max(1, c->cu_count);
-                    const bool lanes = std::min(k2.lane_from_depth, k2.shadow_lane_from) < k2.maxBounces;
-                    hk = std::max(16, k2.tiles / (per_cu <= 40 ? 25 : 200));
-                    hp = per_cu <= 20 ? 16 : per_cu <= 40 ? 8 : lanes ? 2 : 4;
-                }
-            }
-            const bool stamps_fit =  // timed frames split only with a record per part
-                !c->tile_times ||
-                c->tile_times_cap >= static_cast<size_t>(k2.tiles) + static_cast<size_t>(std::min(hk, k2.tiles)) * hp;
-            // In latency mode a dispatch that records wall-time costs runs every tile whole:
-            // a split tile's parts run side by side, so no sum or maximum of theirs stands for
-            // the whole tile's time, and a split set ranked by such an estimate locks in
-            // whatever tiles were split first (the car's waited frame settled at 0.222 or
-            // 0.237 ms by the split set it started from, r04z5). Recording whole tiles every
-            // 16th frame keeps the split set the longest whole tiles. The all-packet frames'
-            // own split (8 waves, above) stays on their cost frames: whole, those took 1.5x
-            // (config 2, the MT car; r04zz profiles), and in flight the ranking matters less.
-            const bool whole = k2.tile_cost && c->cost_time != 0 && !c->tile_times && latency &&
-                               !(c->moving && c->moving_split);
-            // a supersampled frame's bands hold whole n x n blocks of lanes (8 / hp rows >= n),
-            // or the tile is not split: its store reduces each block within one wave
-            const bool blocks_whole = !ss_fused || hp * k2.ss <= 8;
-            if (stamps_fit && hp > 1 && hk > 0 && !whole && blocks_whole) {
-                k2.heavy_k = std::min(hk, k2.tiles);
-                k2.heavy_parts = hp;
-            }
-        }
-        // the cost measure: explicit (rt_debug_cost_time) or the waves' wall time
-        k2.cost_time = c->cost_time != 0 ? 1 : 0;
-        k2.heavy_acc = nullptr;
-        if (k2.tile_cost && k2.heavy_k > 0) {  // the split tiles' part sums and counts (kernel comment)
-            const size_t need = static_cast<size_t>(k2.heavy_k);
-            if (c->heavy_acc_cap < need) {
-                hipFree(c->heavy_acc);
-                c->heavy_acc = nullptr;
-                c->heavy_acc_cap = 0;
-                if (hipMalloc(&c->heavy_acc, need * sizeof(unsigned long long)) != hipSuccess) return RT_ERR_NO_MEMORY;
-                c->heavy_acc_cap = need;
-            }
-            HIP_TRY(hipMemsetAsync(c->heavy_acc, 0, need * sizeof(unsigned long long), c->stream));
-            k2.heavy_acc = c->heavy_acc;
-        }
-        const AccelPtrs A = accel_ptrs(c);
-        // compaction: bounces >= tail_from of the rays still alive run in k_accel_tail
-        k2.tail_queue = nullptr;
-        // RT_TAIL_AUTO: from bounce 2 on scenes of many scene-tree items (measured: config 5's
-        // incoherent bounces -5 %; on the car's 1,302 items the extra kernel costs +18 %)
-        const int tail_from = c->tail_from != RT_TAIL_AUTO
-                                  ? c->tail_from
-                                  : (c->accel.st.item_ref.size() >= kTailAutoItems ? 2 : 0);
-        // the queue's pixel word is row * width + x in 32 bits (rt_device.h): larger
-        // frames render without compaction
-        // Supersampled frames render without it too: k_accel_tail finishes pixels one ray
-        // at a time and cannot take part in the block reduction (same image either way)
-        const bool tail = tail_from > 0 && tail_from < k2.maxBounces && !ss_fused &&
-                          static_cast<unsigned long long>(k2.width) * k2.out_rows < (1ull << 32);
-        const int rx = (k2.tiles_x + 7) / 8, regions = rx * ((k2.tiles / k2.tiles_x + 7) / 8);
-        if (tail) {
-            const size_t need = static_cast<size_t>(regions) * kTailRegion;
-            if (need > c->tail_cap) {
-                hipFree(c->tail_queue);
-                c->tail_queue = nullptr;
-                c->tail_cap = 0;
-                // 3 float4 records, then the pixel words (rt_device.h, tail_queue)
-                if (hipMalloc(&c->tail_queue, need * (3 * sizeof(float4) + sizeof(int))) != hipSuccess)
-                    return RT_ERR_NO_MEMORY;
-                c->tail_cap = need;
-            }
-            if (regions > c->tail_regions_cap) {
-                hipFree(c->tail_counts);
-                c->tail_counts = nullptr;
-                c->tail_regions_cap = 0;
-                if (hipMalloc(&c->tail_counts, 2 * static_cast<size_t>(regions) * sizeof(int)) != hipSuccess)
-                    return RT_ERR_NO_MEMORY;
-                HIP_TRY(hipMemsetAsync(c->tail_counts, 0, 2 * static_cast<size_t>(regions) * sizeof(int), c->stream));
-                c->tail_regions_cap = regions;
-            }
-            k2.tail_queue = c->tail_queue;
-            k2.tail_px = reinterpret_cast<int*>(c->tail_queue + 3 * c->tail_cap);
-            k2.tail_count = c->tail_counts + c->tail_parity * c->tail_regions_cap;
-            k2.tail_count_next = c->tail_counts + (1 - c->tail_parity) * c->tail_regions_cap;
-            k2.tail_from = tail_from;
-            k2.tail_rx = rx;
-            k2.tail_regions = regions;
-            k2.tail_counters = c->tail_regions_cap;
-            k2.tail_max_lanes = c->tail_max_lanes;
-        }
-        // The k_accel instance <TIMED, COST, TAIL, MT, REC, QUEUE>. A dispatch that records
-        // no tile work runs without the walk counters (COST); one that records wall-time
-        // costs (cost_time) records them without counters (REC alone).
-        auto kfn = k_accel<false>;  // records the walk counters as the tiles' costs
-        if (c->accel.mt) {
-            // Moller-Trumbore accelerator: its own instances; no compaction
-            k2.tail_queue = nullptr;
-            kfn = !k2.tile_cost  ? k_accel<false, false, false, true>
-                  : k2.cost_time ? k_accel<false, false, false, true, true>
-                                 : k_accel<false, true, false, true>;
-        } else if (c->tile_times) {
-            // per-tile records (rt_debug_tile_times): counters on, no compaction
-            k2.tail_queue = nullptr;
-            kfn = k_accel<true>;
-        } else if (tail) {
-            // the compacting instance, with the split walks of sparse waves (lane_walk_any)
-            // that the production instance leaves out for its registers
-            kfn = !k2.tile_cost  ? k_accel<false, false, true>
-                  : k2.cost_time ? k_accel<false, false, true, false, true>
-                                 : k_accel<false, true, true>;
-        } else if (latency) {
-            // latency mode without compaction (tail_from 0): the same split walks, without
-            // the queue's code
-            kfn = !k2.tile_cost  ? k_accel<false, false, true, false, false, false>
-                  : k2.cost_time ? k_accel<false, false, true, false, true, false>
-                                 : k_accel<false, true, true, false, true, false>;
-        } else if (!k2.tile_cost) {
-            kfn = k_accel<false, false>;  // production
-        } else if (k2.cost_time) {
-            kfn = k_accel<false, false, false, false, true>;  // production, recording wall time
-        }
-        if (ss_fused) {
-            // the same choice among the supersampling instances (SS): no compaction, no records
-            if (c->accel.mt)
-                kfn = !k2.tile_cost  ? k_accel<false, false, false, true, false, false, true>
-                      : k2.cost_time ? k_accel<false, false, false, true, true, false, true>
-                                     : k_accel<false, true, false, true, true, false, true>;
-            else if (latency)
-                kfn = !k2.tile_cost  ? k_accel<false, false, true, false, false, false, true>
-                      : k2.cost_time ? k_accel<false, false, true, false, true, false, true>
-                                     : k_accel<false, true, true, false, true, false, true>;
-            else
-                kfn = !k2.tile_cost  ? k_accel<false, false, false, false, false, false, true>
-                      : k2.cost_time ? k_accel<false, false, false, false, true, false, true>
-                                     : k_accel<false, true, false, false, true, false, true>;
-        }
-        if (k2.rgb >= RT_FORMAT_RGBA8) {
-            // a display format: the chosen instance's twin, compiled with the conversion
-            auto twin = decltype(kfn){nullptr};
-            for (const AccelTwin& t : kAccelTwins)
-                if (t.plain == kfn) twin = t.display;
-            if (!twin) return RT_ERR_INVALID;  // an instance without a twin: kAccelTwins is out of date
-            kfn = twin;
-        }
-        const bool tail_on = k2.tail_queue != nullptr;
-        // one wave per dispatch slot: the split heavy tiles' extra waves too
-        const int blocks = k2.tiles + k2.heavy_k * (k2.heavy_parts - 1);
-        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(64), lds, c->stream, A, c->mat, k2);
-        if (tail_on) {
-            const size_t tlds = static_cast<size_t>(k2.lane_stack) * 64 * 6;
-            const int tgrid = regions * (kTailRegion / 64);  // one wave per possible chunk
-            hipLaunchKernelGGL(k_accel_tail, dim3(tgrid), dim3(64), tlds, c->stream, A, c->mat, k2);
-            c->tail_parity = 1 - c->tail_parity;
-        }
-        if (filter) launch_box_filter(c, kin);
-        if (ad_fast) {
-            KParams smp = kin;  // the sample frame, walked per lane
-            smp.lane_stack = k2.lane_stack;
-            launch_adaptive(c, A, kout, smp);
-        }
-        if (k2.tile_cost) {
-            // the next frame's order; stream-ordered after this dispatch (and after its
-            // end event, so rt_kernel_times is the render kernel alone), before the next
-            if (rec) HIP_TRY(hipEventRecord(e1, c->stream));
-            order_after = true;
-            const unsigned* set = c->sched_sets + c->sched_parity * sched_set_words(c->sched_cap);
-            unsigned* next = c->sched_sets + (1 - c->sched_parity) * sched_set_words(c->sched_cap);
-            const int groups = (k2.tiles + kOrderThreads - 1) / kOrderThreads;
-            const unsigned* cost = c->sched_cost;
-            if (latency && c->frame_event) {
-                // a waited frame ends here (rt_sync_frame); the order runs behind it on the same
-                // stream, within the host's turnaround to the next dispatch
-                if (!c->frame_ev && hipEventCreateWithFlags(&c->frame_ev, hipEventDisableTiming) != hipSuccess)
-                    return RT_ERR_DEVICE;
-                HIP_TRY(hipEventRecord(c->frame_ev, c->stream));
-                c->frame_ev_set = true;
-            }
-            if (dilate > 0) {
-                const size_t need = static_cast<size_t>(k2.tiles) + static_cast<size_t>(groups) * kOrderBuckets;
-                if (c->dil_cap < need) {
-                    hipFree(c->dil_cost);
-                    c->dil_cost = nullptr;
-                    c->dil_cap = 0;
-                    if (hipMalloc(&c->dil_cost, need * sizeof(unsigned)) != hipSuccess) return RT_ERR_NO_MEMORY;
-                    c->dil_cap = need;
-                }
-                hipLaunchKernelGGL(k_cost_dilate, dim3(groups), dim3(kOrderThreads), 0, c->stream, c->sched_cost,
-                                   k2.tiles, k2.tiles_x, dilate, c->dil_cost, c->dil_cost + k2.tiles);
-                cost = c->dil_cost;
-                set = c->dil_cost + k2.tiles;
-            }
-            hipLaunchKernelGGL(k_tile_order, dim3(groups), dim3(kOrderThreads),
-                               0, c->stream, cost, k2.tiles, set, next,
-                               static_cast<int>(sched_set_words(c->sched_cap)), c->sched_order,
-                               c->schedule == RT_SCHED_COST_XCD ? 1 : 0);
-            c->sched_parity = 1 - c->sched_parity;
-            c->sched_valid = k2.tiles;
-        }
+        // (on cost frames the span ends between the render and the order kernels: mark_end)
+        if (const int rc = launch_accel(c, kin, kout, kp, sp, rec ? &span : nullptr)) return rc;
     } else {
         hipLaunchKernelGGL(k_packet, grid, dim3(kBlock), 0, c->stream, c->geo_leaf, c->geo_lin, c->mat, c->nodes,
                            kp);
-        if (filter) launch_box_filter(c, kin);
+        if (sp.filter) launch_box_filter(c, kin);
     }
     c->last_kind = stats ? RT_KERNEL_LANE : kind;
     HIP_TRY(hipGetLastError());
     if (rec) {
-        if (!order_after) HIP_TRY(hipEventRecord(e1, c->stream));
-        c->last0 = e0;
-        c->last1 = e1;
-        if (c->ring_used < static_cast<int>(c->ring0.size())) ++c->ring_used;
-        c->timed = true;
+        if (const int rc = end_timed(c, span)) return rc;
     } else if (!stats) {
         c->timed = false;  // rt_set_kernel_timing(0): rt_last_kernel_ms has no dispatch to report
     }
@@ -5803,32 +5733,19 @@ int trace_launch(rt_ctx* c, const float4* rays, const int2* xy, int n, float4* h
     const bool mt = c->params.useMollerTrumbore != 0;
     KParams kp;
     std::memset(&kp, 0, sizeof kp);
-    kp.geo_leaf = t->geo_leaf;
-    kp.geo_lin = t->geo_lin;
-    kp.nodes = t->nodes;
-    kp.S = t->S;
-    kp.N = t->N;
-    kp.I = t->I;
-    kp.max_stack = t->max_stack < 1 ? 1 : t->max_stack;
+    scene_params(t, kp);
     kp.useBVH = 1;
     kp.useMT = mt ? 1 : 0;
-    kp.lane_stack = t->lane_stack_override > 0 ? t->lane_stack_override : t->accel.max_stack;
-    if (xy) {
-        fill_camera(c->cam, kp);
-        kp.resX = c->params.resX;
-        kp.resY = c->params.resY;
-    }
+    if (xy) camera_params(c, kp);
     const TraceArgs q{rays, xy, hits, n};
     const bool any = mode == RT_TRACE_ANY;
     if (accel) {
         auto kfn = mt ? (any ? k_trace<RT_TRACE_ANY, true> : k_trace<RT_TRACE_CLOSEST, true>)
                       : (any ? k_trace<RT_TRACE_ANY, false> : k_trace<RT_TRACE_CLOSEST, false>);
-        const size_t lds = static_cast<size_t>(kp.lane_stack) * 64 * 6;
-        hipLaunchKernelGGL(kfn, dim3((n + 63) / 64), dim3(64), lds, c->stream, accel_ptrs(t), q, kp);
+        hipLaunchKernelGGL(kfn, dim3((n + 63) / 64), dim3(64), lane_stack_lds(kp), c->stream, accel_ptrs(t), q, kp);
     } else {
         auto kfn = any ? k_trace_ref<RT_TRACE_ANY> : k_trace_ref<RT_TRACE_CLOSEST>;
-        const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
-        hipLaunchKernelGGL(kfn, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, c->stream, q, kp);
+        hipLaunchKernelGGL(kfn, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), ref_stack_lds(kp), c->stream, q, kp);
     }
     HIP_TRY(hipGetLastError());
     return RT_OK;
@@ -5868,12 +5785,20 @@ int trace_staged(rt_ctx* c, const void* in, size_t in_bytes, bool pixels, int n,
 // (tools/bench_gbuffer.py's a_w2 and a_w4, DESIGN.md §4 "Geometry buffers").
 constexpr int kGbufWaves = 1;
 
+// A per-pixel plane dispatch's row mapping (as fill_kparams checks a frame's) and its size: a
+// grid of tile rows the launch can have, and row * width + x in 32 bits.
+bool plane_rows_ok(int width, int height, int y0, int stripe, int period, int out_rows) {
+    return width > 0 && height > 0 && stripe > 0 && period >= stripe && out_rows >= 0 && y0 >= 0 &&
+           (static_cast<long long>(out_rows) + kTileH - 1) / kTileH <= 65535 &&
+           static_cast<unsigned long long>(width) * static_cast<unsigned long long>(out_rows) < (1ull << 32);
+}
+
 int gbuffer_check(const rt_ctx* c, int width, int height, int y0, int stripe, int period, int out_rows,
                   const rt_gbuffer* out, bool* run) {
     *run = false;
     if (!c || !out || (!out->shape && !out->depth && !out->normal && !out->position)) return RT_ERR_INVALID;
     if (!c->have_scene || !c->have_cam || !c->have_params) return RT_ERR_NO_SCENE;
-    if (width <= 0 || height <= 0 || stripe <= 0 || period < stripe || out_rows < 0 || y0 < 0) return RT_ERR_INVALID;
+    if (!plane_rows_ok(width, height, y0, stripe, period, out_rows)) return RT_ERR_INVALID;
     const struct {
         const void* p;
         size_t pitch, px;
@@ -5885,9 +5810,6 @@ int gbuffer_check(const rt_ctx* c, int width, int height, int y0, int stripe, in
         if (pl.p && (pl.pitch < static_cast<size_t>(width) * pl.px || pl.pitch % pl.px != 0 ||
                      reinterpret_cast<uintptr_t>(pl.p) % pl.px != 0))
             return RT_ERR_INVALID;
-    if ((static_cast<long long>(out_rows) + kTileH - 1) / kTileH > 65535 ||
-        static_cast<unsigned long long>(width) * static_cast<unsigned long long>(out_rows) >= (1ull << 32))
-        return RT_ERR_INVALID;
     *run = out_rows > 0;
     return RT_OK;
 }
@@ -5898,19 +5820,10 @@ KParams plane_params(const rt_ctx* c, const rt_ctx* t, int width, int height, in
                      int out_rows) {
     KParams kp;
     std::memset(&kp, 0, sizeof kp);
-    kp.geo_leaf = t->geo_leaf;
-    kp.geo_lin = t->geo_lin;
-    kp.nodes = t->nodes;
-    kp.S = t->S;
-    kp.N = t->N;
-    kp.I = t->I;
-    kp.max_stack = t->max_stack < 1 ? 1 : t->max_stack;
+    scene_params(t, kp);
     kp.useBVH = 1;
     kp.useMT = c->params.useMollerTrumbore != 0 ? 1 : 0;
-    kp.lane_stack = t->lane_stack_override > 0 ? t->lane_stack_override : t->accel.max_stack;
-    fill_camera(c->cam, kp);
-    kp.resX = c->params.resX;
-    kp.resY = c->params.resY;
+    camera_params(c, kp);
     kp.width = width;
     kp.height = height;
     kp.y0 = y0;
@@ -5920,21 +5833,6 @@ KParams plane_params(const rt_ctx* c, const rt_ctx* t, int width, int height, in
     kp.tiles_x = (width + 7) / 8;
     kp.tiles = kp.tiles_x * ((out_rows + 7) / 8);
     return kp;
-}
-
-// The root's current bounds, as launch() passes them to k_accel (the tile kernels' sky skip).
-void plane_root(const rt_ctx* t, KParams& kp) {
-    if (kp.N > 0 && t->nodes_on_device_newer) kp.root_ok = 2;
-    if (kp.N > 0 && !t->nodes_on_device_newer && static_cast<int>(t->host_nodes.size()) == kp.N) {
-        const FlatNode& rn = t->host_nodes[kp.N - 1];
-        kp.root_ok = 1;
-        kp.root_lo[0] = rn.boundsMin.x;
-        kp.root_lo[1] = rn.boundsMin.y;
-        kp.root_lo[2] = rn.boundsMin.z;
-        kp.root_hi[0] = rn.boundsMax.x;
-        kp.root_hi[1] = rn.boundsMax.y;
-        kp.root_hi[2] = rn.boundsMax.z;
-    }
 }
 
 // One geometry-buffer launch on the context's stream: pending scene writes first, as one
@@ -5950,22 +5848,21 @@ int gbuffer_launch(rt_ctx* c, int width, int height, int y0, int stripe, int per
     KParams kp = plane_params(c, t, width, height, y0, stripe, period, out_rows);
     if (!accel) {
         const dim3 grid((width + kTileW - 1) / kTileW, (out_rows + kTileH - 1) / kTileH);
-        const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
-        hipLaunchKernelGGL(k_gbuffer_ref, grid, dim3(kBlock), lds, c->stream, g, kp);
+        hipLaunchKernelGGL(k_gbuffer_ref, grid, dim3(kBlock), ref_stack_lds(kp), c->stream, g, kp);
         HIP_TRY(hipGetLastError());
         return RT_OK;
     }
-    plane_root(t, kp);
+    root_bounds(t, kp);  // whatever maxBounces says (plane_params leaves it 0): the camera ray is always traced
     // the packet form needs the shared origin inside the accelerator's bound (accel_usable)
     const float cmag = std::max({std::fabs(kp.cam_pos.x), std::fabs(kp.cam_pos.y), std::fabs(kp.cam_pos.z)});
     const bool lane = c->gbuf_walk == 1 || !(cmag <= t->accel.origin_lim);
     int waves = c->gbuf_waves > 0 ? c->gbuf_waves : kGbufWaves;
     // the lane form's stacks (lane_stack x 6 B a lane) within the 64 KB a block may ask for
-    while (lane && waves > 1 && static_cast<size_t>(kp.lane_stack) * 64 * waves * 6 > 65536) waves /= 2;
+    while (lane && waves > 1 && lane_stack_lds(kp) * waves > 65536) waves /= 2;
     const dim3 grid((kp.tiles + waves - 1) / waves), block(64 * waves);
     auto kfn = lane ? (mt ? k_gbuffer<true, true> : k_gbuffer<false, true>)
                     : (mt ? k_gbuffer<true, false> : k_gbuffer<false, false>);
-    const size_t lds = lane ? static_cast<size_t>(kp.lane_stack) * block.x * 6 : 0;  // the packet form: no LDS
+    const size_t lds = lane ? lane_stack_lds(kp) * waves : 0;  // the packet form: no LDS
     hipLaunchKernelGGL(kfn, grid, block, lds, c->stream, accel_ptrs(t), g, kp);
     HIP_TRY(hipGetLastError());
     return RT_OK;
@@ -5985,16 +5882,13 @@ int ao_check(const rt_ctx* c, int width, int height, int y0, int stripe, int per
     *run = false;
     if (!c || !p || !out || (!out->count && !out->visibility)) return RT_ERR_INVALID;
     if (!c->have_scene || !c->have_cam || !c->have_params) return RT_ERR_NO_SCENE;
-    if (width <= 0 || height <= 0 || stripe <= 0 || period < stripe || out_rows < 0 || y0 < 0) return RT_ERR_INVALID;
+    if (!plane_rows_ok(width, height, y0, stripe, period, out_rows)) return RT_ERR_INVALID;
     if (p->rays < 1 || p->rays > 64 || !(p->radius > 0.0f) || !(p->bias >= 0.0f) || std::isinf(p->bias) ||
         p->reserved != 0)
         return RT_ERR_INVALID;
     if (out->count && out->count_pitch < static_cast<size_t>(width)) return RT_ERR_INVALID;
     if (out->visibility && (out->visibility_pitch < static_cast<size_t>(width) * 4 || out->visibility_pitch % 4 != 0 ||
                             reinterpret_cast<uintptr_t>(out->visibility) % 4 != 0))
-        return RT_ERR_INVALID;
-    if ((static_cast<long long>(out_rows) + kTileH - 1) / kTileH > 65535 ||
-        static_cast<unsigned long long>(width) * static_cast<unsigned long long>(out_rows) >= (1ull << 32))
         return RT_ERR_INVALID;
     *run = out_rows > 0;
     return RT_OK;
@@ -6014,16 +5908,15 @@ int ao_launch(rt_ctx* c, int width, int height, int y0, int stripe, int period, 
     const AoArgs q{out, p.rays, p.radius, p.bias};
     if (!accel) {
         const dim3 grid((width + kTileW - 1) / kTileW, (out_rows + kTileH - 1) / kTileH);
-        const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
-        hipLaunchKernelGGL(k_ao_ref, grid, dim3(kBlock), lds, c->stream, q, kp);
+        hipLaunchKernelGGL(k_ao_ref, grid, dim3(kBlock), ref_stack_lds(kp), c->stream, q, kp);
         HIP_TRY(hipGetLastError());
         return RT_OK;
     }
-    plane_root(t, kp);
+    root_bounds(t, kp);
     const float cmag = std::max({std::fabs(kp.cam_pos.x), std::fabs(kp.cam_pos.y), std::fabs(kp.cam_pos.z)});
     const bool lane = !(cmag <= t->accel.origin_lim);
     const bool pack = c->ao_form == 0 ? kAoPack : c->ao_form == 1;
-    const size_t per_wave = static_cast<size_t>(kp.lane_stack) * 64 * 6 + (pack ? kAoSlot * 64 * sizeof(int) : 0);
+    const size_t per_wave = lane_stack_lds(kp) + (pack ? kAoSlot * 64 * sizeof(int) : 0);
     int waves = c->ao_waves > 0 ? c->ao_waves : kAoWaves;
     while (waves > 1 && per_wave * waves > 65536) waves /= 2;  // within the 64 KB a block may ask for
     const dim3 grid((kp.tiles + waves - 1) / waves), block(64 * waves);
@@ -6059,7 +5952,7 @@ int shade_check(const rt_ctx* c, const void* rays, int n, const void* pixels, in
 // profiles/shade_bench.jsonl), split against plain: the car (1,293 items) 0.376 against
 // 0.365 ms, +3 %; 100k triangles 4.514 against 4.555 ms, -1 %; the monkey scene +3 %.
 // Moller-Trumbore lists always take the plain instance, as every MT frame does.
-constexpr size_t kShadeSplitItems = kTailAutoItems;
+constexpr size_t kShadeSplitItems = rtp::kTailAutoItems;
 
 // One shading launch on the context's stream: pending scene writes first, as one refit; then
 // the context render_frame would take the frame to -- the brute sub-context for useBVH = 0
@@ -6076,9 +5969,7 @@ int shade_launch(rt_ctx* c, const float4* rays, int n, void* pixels, int format)
     sel.useMT = c->params.useMollerTrumbore;
     float off = 1e-3f;
     for (int hop = 0; hop < 2; ++hop) {
-        rt_ctx* nxt = brute_ctx(t, sel);
-        if (nxt) off = 1e-5f;  // gpu_shader.comp:565
-        else nxt = mt_ctx(t, sel);
+        rt_ctx* nxt = next_hop(t, sel, off);
         if (!nxt) break;
         sel.useBVH = nxt->params.useBVH;
         sel.useMT = nxt->params.useMollerTrumbore;
@@ -6093,14 +5984,8 @@ int shade_launch(rt_ctx* c, const float4* rays, int n, void* pixels, int format)
     }
     KParams kp;
     std::memset(&kp, 0, sizeof kp);
-    kp.geo_leaf = t->geo_leaf;
-    kp.geo_lin = t->geo_lin;
+    scene_params(t, kp);
     kp.mat = t->mat;
-    kp.nodes = t->nodes;
-    kp.S = t->S;
-    kp.N = t->N;
-    kp.I = t->I;
-    kp.max_stack = t->max_stack < 1 ? 1 : t->max_stack;
     kp.light_pos = V{c->light.position.x, c->light.position.y, c->light.position.z};
     kp.light_color = V{c->light.color.x, c->light.color.y, c->light.color.z};
     kp.maxBounces = c->params.maxBounces;
@@ -6117,19 +6002,16 @@ int shade_launch(rt_ctx* c, const float4* rays, int n, void* pixels, int format)
     const ShadeArgs q{rays, n};
     const bool disp = format >= RT_FORMAT_RGBA8;
     if (accel) {
-        kp.lane_stack = t->lane_stack_override > 0 ? t->lane_stack_override : t->accel.max_stack;
         const bool split = !mt && (c->shade_split ? c->shade_split == 2 : t->accel.st.item_ref.size() >= kShadeSplitItems);
         auto kfn = mt      ? (disp ? k_shade<true, false, true> : k_shade<true, false, false>)
                    : split ? (disp ? k_shade<false, true, true> : k_shade<false, true, false>)
                            : (disp ? k_shade<false, false, true> : k_shade<false, false, false>);
-        const size_t lds = static_cast<size_t>(kp.lane_stack) * 64 * 6;
-        hipLaunchKernelGGL(kfn, dim3((static_cast<unsigned>(n) + 63u) / 64u), dim3(64), lds, c->stream, accel_ptrs(t),
-                           t->mat, q, kp);
+        hipLaunchKernelGGL(kfn, dim3((static_cast<unsigned>(n) + 63u) / 64u), dim3(64), lane_stack_lds(kp), c->stream,
+                           accel_ptrs(t), t->mat, q, kp);
     } else {
         auto kfn = disp ? k_shade_ref<true> : k_shade_ref<false>;
-        const size_t lds = static_cast<size_t>(kp.max_stack) * kBlock * sizeof(int);
-        hipLaunchKernelGGL(kfn, dim3((static_cast<unsigned>(n) + kBlock - 1u) / kBlock), dim3(kBlock), lds, c->stream, q,
-                           kp);
+        hipLaunchKernelGGL(kfn, dim3((static_cast<unsigned>(n) + kBlock - 1u) / kBlock), dim3(kBlock), ref_stack_lds(kp),
+                           c->stream, q, kp);
     }
     HIP_TRY(hipGetLastError());
     return RT_OK;
@@ -6147,9 +6029,7 @@ int camera_rays_check(const rt_ctx* c, int width, int height, int y0, int rows, 
 int camera_rays_launch(rt_ctx* c, int width, int height, int y0, int rows, float4* out) {
     KParams kp;
     std::memset(&kp, 0, sizeof kp);
-    fill_camera(c->cam, kp);
-    kp.resX = c->params.resX;
-    kp.resY = c->params.resY;
+    camera_params(c, kp);
     kp.width = width;
     kp.height = height;
     kp.y0 = y0;

@@ -360,6 +360,32 @@ def test_mt_heavy_tiles_split_equals_literal(ctx, k, parts):
         ctx.debug_heavy(-1, 4)
 
 
+@pytest.mark.parametrize("measure", [0, 1], ids=["counters", "wall_time"])
+def test_mt_cost_frame_and_ordered_frame_equal_literal(ctx, measure):
+    """The MT k_accel instances by what the dispatch records: a cost frame by either measure
+    (rt_debug_cost_time), then a frame in the order it left, which records nothing; both equal
+    the literal k_packet MT frame bit for bit. 76 x 44: 10 x 6 tiles, a partial column and row."""
+    W, H = 76, 44
+    fs = rtamd.generate(3, 0, W, H)
+    lit = render_mt(ctx, fs, W, H, 3, True, rtamd.KERNEL_PACKET)
+    try:
+        ctx.debug_cost_time(measure)
+        ctx.upload(fs)
+        ctx.set_params(W, H, 3, True, False, True)
+        ctx.set_kernel(rtamd.KERNEL_AUTO)
+        for period, what in [(1, "cost frame"), (16, "ordered frame")]:  # period 1: every dispatch a cost frame
+            ctx.debug_sched_period(period)
+            out = torch.full((H, W, 4), float("nan"), dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+            ctx.dispatch_rows(W, H, 0, 1, 1, H, out.data_ptr(), W * 16)
+            ctx.sync()
+            assert ctx.accel_info()["last_kernel"] == rtamd.KERNEL_ACCEL
+            assert np.array_equal(out.cpu().numpy(), lit), what
+    finally:
+        ctx.debug_sched_period(16)
+        ctx.debug_cost_time(-1)
+
+
 def test_mt_vs_oracle_band(ctx):
     W, H = 1920, 1080
     fs = rtamd.generate(3, 0, W, H)

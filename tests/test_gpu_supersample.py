@@ -246,6 +246,31 @@ def test_uniforms_that_change_the_frame(ctx, n, s):
         assert ctx.accel_info()["last_kernel"] == rtamd.KERNEL_ACCEL
 
 
+@pytest.mark.parametrize("measure", [0, 1], ids=["counters", "wall_time"])
+@pytest.mark.parametrize("case", ["plain", "latency", "moller_trumbore"])
+def test_cost_frames_and_ordered_frames(ctx, case, measure):
+    """The supersampling k_accel instances by what the dispatch records: a cost frame (by
+    either measure, rt_debug_cost_time) and then a frame in the order it left, which records
+    nothing, in the default mode, in latency mode and over the Moller-Trumbore accelerator.
+    76 x 44 at 2 x 2: 19 x 11 sample tiles with a partial column."""
+    W, H, n = 76, 44, 2
+    s = (3, True, False, True) if case == "moller_trumbore" else PLAIN3
+    ref = gpu_box(ctx, 3, W, H, n, s, rtamd.KERNEL_ACCEL)
+    load(ctx, scene(3, n * W, n * H), W, H, s, rtamd.KERNEL_ACCEL)
+    try:
+        ctx.debug_cost_time(measure)
+        ctx.set_latency_mode(case == "latency")
+        ctx.debug_sched_period(1)  # every dispatch a cost frame
+        same(full_frame(ctx, W, H, n), ref, f"{case} measure {measure}: cost frame")
+        assert ctx.accel_info()["last_kernel"] == rtamd.KERNEL_ACCEL
+        ctx.debug_sched_period(16)
+        same(full_frame(ctx, W, H, n), ref, f"{case} measure {measure}: ordered frame")
+        assert ctx.accel_info()["last_kernel"] == rtamd.KERNEL_ACCEL
+    finally:
+        ctx.debug_sched_period(16)
+        ctx.debug_cost_time(-1)
+
+
 # --------------------------------------------------------------------------
 # 4. row forms and formats
 @pytest.mark.parametrize("kernel", [rtamd.KERNEL_ACCEL, rtamd.KERNEL_PACKET], ids=KNAME.get)
