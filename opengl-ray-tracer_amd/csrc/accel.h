@@ -112,8 +112,8 @@ struct AccelHost {
     std::vector<float> lmt;
     float mt_z[3] = {0.f, 0.f, 0.f};
     // Per shape, its class and conservative box (classify with origin_lim) as built, then
-    // as prepare_animation last classified it (shapes written since the build): the refit's
-    // fixed slot boxes reuse them (rt_kernels.hip prepare_animation; classifying 100k
+    // as plan_refit last classified it (shapes written since the build): the refit's
+    // fixed slot boxes reuse them (refit_plan.h plan_refit, ShapeCache; classifying 100k
     // shapes again took ~40 ms of a config-5 refit setup).
     std::vector<int> shape_cls;
     std::vector<Box3> shape_box;
@@ -134,7 +134,7 @@ void parallel_for(int n, int min_per_thread, const std::function<void(int, int)>
 
 // The prim range [first, end) below every local node (a subtree's prims are contiguous:
 // LocalBuilder emits them together; false if they are not) and below every scene-tree
-// node, for the refit's slot lists (rt_kernels.hip prepare_animation) and its dump.
+// node, for the refit's slot lists (refit_plan.h plan_refit) and its dump.
 bool local_prim_ranges(const AccelHost& A, std::vector<int>& first, std::vector<int>& end);
 void scene_prim_ranges(const SceneTree& T, std::vector<int>& first, std::vector<int>& end);
 // Per wide slot 4*w + s of the device's wide records (the local ones, then the scene

@@ -80,6 +80,8 @@
 #include "../../include/rt_api.h"
 #include "accel.h"
 #include "accel_math.h"
+#include "accel_pack.h"
+#include "refit_plan.h"
 #include "lbvh.h"
 #include "rt_device.h"
 #include "ao_table.h"
@@ -94,9 +96,10 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kTileW = 32;  // pixels per block row (4 waves x 8)
 constexpr int kTileH = 8;
-constexpr int kMaxStack = 64;  // gpu_shader.comp:384
-constexpr int kRing = 1024;
-constexpr int kLeafScan = 8;   // leaves with more shapes get a local BVH (accel.h)    // dispatch timings kept between rt_kernel_times calls
+constexpr int kRing = 1024;    // dispatch timings kept between rt_kernel_times calls
+// the device layout's codes, strides and thresholds, shared with the host packer (accel_codes.h)
+using rta::kMaxStack, rta::kLeafScan, rta::kLocal, rta::kLeaf, rta::kTopLeaf, rta::kItem, rta::kPair, rta::kRecMask,
+    rta::kNoChild, rta::kWideRec, rta::kWideRecMt, rta::kBigList, rta::bits_f, rta::PhaseLaps;
 
 // Stats slots, in rt_stats field order.
 enum {
@@ -627,12 +630,6 @@ struct AccelPtrs {
     float mt_z[3];                      // AccelHost::mt_z (Moller-Trumbore per-ray padding)
 };
 
-// Child codes of the walks' stacks and of lnodes / wnodes entries.
-constexpr unsigned kLocal = 0x80000000u, kLeaf = 0x40000000u, kTopLeaf = 0x20000000u, kItem = 0x10000000u;
-// A wide-node code (kLocal without kLeaf) with kPair names a node of two consecutive
-// records (accel.h kWideKids, AccelHost::wpair): both are tested at one step.
-constexpr unsigned kPair = 0x08000000u, kRecMask = 0x07ffffffu;
-constexpr int kNoChild = 0x7fffffff;
 constexpr bool kWide8 = RT_WIDE8 != 0;
 
 // The closest hit so far: distance, rank in the reference walk, ray parameter and
@@ -942,10 +939,6 @@ __device__ __forceinline__ void wide_pair_q(const rta::RayC& c, float tl, f2 lx,
     h1 = (tn[1] <= tf[1]) & !rta::cone_culls_q(w1, c.dq);
 }
 
-// Wide-node record stride in float4: 8 (quantized cones), 17 for the
-// Moller-Trumbore accelerator: boxes (6), float grazing cones (4: axis, s),
-// the per-ray padding constants (6, accel.h AccelHost::lmt) and the codes.
-constexpr int kWideRec = 8, kWideRecMt = 17;
 #ifndef RT_MT_UNROLL
 #define RT_MT_UNROLL 4  // MT wide_kids: children per unrolled step (r03j: 1 -> 4 car MT -15 %)
 #endif
@@ -2924,7 +2917,7 @@ __host__ __device__ void reference_box(const FlatShape& s, float lo[3], float hi
     }
 }
 
-// CSR lists built by prepare_animation on the host. Per animated shape i:
+// CSR lists built on the host (refit_plan.h plan_refit, RefitOffsets). Per animated shape i:
 //   slots  : its geo_leaf slots (bvhIndices positions)
 //   prims  : its accelerator prim slots
 //   wpos   : wide-record slots (4*w + s) of the local nodes above those prims
@@ -3020,7 +3013,6 @@ __device__ __forceinline__ void wave_minmax(float lo[3], float hi[3]) {
 // result); sh: LDS scratch of the workgroup, free again on return.
 constexpr int kRefitWaves = 4;
 constexpr long long kDirectReads = 2048;  // rt_ctx::refit_mode auto
-constexpr int kBigList = 256;             // a slot's refit list a wave unions in one step
 __device__ __forceinline__ void block_minmax(float lo[3], float hi[3], float (*sh)[6]) {
     wave_minmax(lo, hi);
     const int nw = blockDim.x >> 6;
@@ -3949,44 +3941,36 @@ int check_tree(const FlatNode* nodes, int N, const int* idx, int I, int S, int* 
     return RT_OK;
 }
 
-inline float bits_f(int v) {
-    float f;
-    std::memcpy(&f, &v, sizeof f);
-    return f;
-}
-
 // Builds the accelerator from the host copies of the scene and uploads it;
 // expects geo_lin to be packed (k_pack_prims copies from it). On failure the
 // context keeps rendering with k_packet.
-// Diagnostics (RT_REBUILD_PROFILE set): wall time of the phases of a host step on
-// stderr, each lap since the previous one.
-struct PhaseLaps {
-    const char* step;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    explicit PhaseLaps(const char* s) : step(s) {}
-    void operator()(const char* what) {
-        static const bool on = std::getenv("RT_REBUILD_PROFILE") != nullptr;
-        if (!on || !step) return;  // (a null step: this instance reports nothing)
-        const auto t = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "%s %-24s %8.3f ms\n", step, what, std::chrono::duration<double, std::milli>(t - t0).count());
-        t0 = t;
-    }
-};
-
-// A host array left uninitialised: no serial zeroing pass, its pages are first touched
-// by the threads that fill it (config 5's 24 MB of wnodes: 5.4 ms of page faults on one
-// thread). Every element is written before the array is read.
-template <class T>
-struct RawArray {
-    std::unique_ptr<T[]> p;
-    size_t n;
-    explicit RawArray(size_t count) : p(new T[count]), n(count) {}
-    T* data() { return p.get(); }
-    size_t size() const { return n; }
-    T& operator[](size_t i) { return p[i]; }
-};
-
 int upload_built_accel(rt_ctx* c);
+
+// The packed host arrays are the device's float4 / int4 as they stand (accel_pack.h).
+static_assert(sizeof(rta::F4) == sizeof(float4) && alignof(rta::F4) == alignof(float4), "F4 uploads as float4");
+static_assert(sizeof(rta::I4) == sizeof(int4) && alignof(rta::I4) == alignof(int4), "I4 uploads as int4");
+
+// A device array to allocate and the host array it is filled from (null: allocated only).
+struct HostArray {
+    void** dev;
+    const void* src;
+    size_t bytes;
+};
+template <class D, class T>
+HostArray host_array(D*& dev, const T* src, size_t count) {
+    static_assert(sizeof(D) == sizeof(T), "copied element for element");
+    return HostArray{reinterpret_cast<void**>(&dev), src, count * sizeof(D)};
+}
+// Allocates every array, then issues their copies on the context's stream, in order.
+int alloc_and_copy(rt_ctx* c, std::initializer_list<HostArray> arrays, PhaseLaps* lap = nullptr) {
+    for (const HostArray& a : arrays)
+        if (hipMalloc(a.dev, a.bytes) != hipSuccess) return RT_ERR_NO_MEMORY;
+    if (lap) (*lap)("hipMalloc");
+    for (const HostArray& a : arrays)
+        if (a.src) HIP_TRY(hipMemcpyAsync(*a.dev, a.src, a.bytes, hipMemcpyHostToDevice, c->stream));
+    return RT_OK;
+}
+
 // built: the host build already ran (rt_upload_scene overlaps it with the records'
 // device upload) and returned *built; null: build here.
 int build_upload_accel(rt_ctx* c, const bool* built = nullptr) {
@@ -4007,209 +3991,38 @@ int build_upload_accel(rt_ctx* c, const bool* built = nullptr) {
 // current host node records' exact boxes and the device's current shape records.
 int upload_built_accel(rt_ctx* c) {
     PhaseLaps lap("  upload");
-    const int N = c->N;
-    rta::AccelHost& A = c->accel;
-    if (N >= (1 << 28)) return RT_OK;  // codes carry the node index in 28 bits
-    // The arrays below are packed on the build threads (rta::parallel_for): each entry is
-    // written by one thread from read-only inputs.
-    constexpr int kPackChunk = 8192;
-    // anodes: every reference node's exact box and content box (the root's entry test).
-    RawArray<float4> an(4 * static_cast<size_t>(N));
-    std::atomic<int> nan_box{0};
-    rta::parallel_for(N, kPackChunk, [&](int k0, int k1) {
-        int nan = 0;
-        for (int k = k0; k < k1; ++k) {
-            const FlatNode& n = c->host_nodes[k];
-            for (float v : {n.boundsMin.x, n.boundsMin.y, n.boundsMin.z, n.boundsMax.x, n.boundsMax.y, n.boundsMax.z})
-                nan |= std::isnan(v) ? 1 : 0;
-            const rta::Box3& cb = A.content[k];
-            an[4 * k + 0] = make_float4(n.boundsMin.x, n.boundsMin.y, n.boundsMin.z, bits_f(n.leftChild));
-            an[4 * k + 1] = make_float4(n.boundsMax.x, n.boundsMax.y, n.boundsMax.z, bits_f(n.rightChild));
-            an[4 * k + 2] = make_float4(cb.lo[0], cb.lo[1], cb.lo[2], bits_f(A.flags[k]));
-            an[4 * k + 3] = make_float4(cb.hi[0], cb.hi[1], cb.hi[2], 0.f);
-        }
-        if (nan) nan_box.store(1);
-    });
-    c->boxes_finite = nan_box.load() ? 0 : 1;
-    lap("anodes");
-    // lnodes: the wide local nodes (accel.h, build_wide), kWideRec float4 each with
-    // quantized cones (kWideRecMt with the MT accelerator's float grazing cones; wide_kids).
-    const size_t P = A.prim_shape.size();
-    const int rec = A.mt ? kWideRecMt : kWideRec;
-    std::atomic<bool> codes_ok{true};
-    auto leaf_code = [&](size_t j) -> int {
-        const unsigned st = static_cast<unsigned>(-A.la[j] - 1), cnt = static_cast<unsigned>(A.lb[j]);
-        if (st >= (1u << 22) || cnt > 63u) codes_ok.store(false);
-        return static_cast<int>(kLocal | kLeaf | (st << 6) | cnt);
-    };
-    // The scene tree's wide nodes (accel.h, SceneTree) follow the local ones;
-    // its leaves are item codes (kTopLeaf | kItem | item).
-    const rta::SceneTree& T = A.st;
-    const bool use_st = T.wroot >= 0;
-    const size_t nw = A.wchild.size() / rta::kWide;
-    const size_t nws = use_st ? T.wchild.size() / rta::kWide : 0;
-    if (nw + nws >= (1u << 27) || T.item_ref.size() >= (1u << 28)) return RT_OK;  // kRecMask, kItem
-    // the code of the node whose first record is r (+ base): kPair when it spans two
-    auto wide_code = [](const std::vector<char>& pair, int r, size_t base) {
-        return static_cast<int>(kLocal | static_cast<unsigned>(base + r) |
-                                (r < static_cast<int>(pair.size()) && pair[r] ? kPair : 0u));
-    };
-    std::vector<float4> ln(rec * (nw + nws ? nw + nws : 1));
-    auto emit_wide = [&](size_t w, size_t at, const std::vector<int>& wchild, const std::vector<int>& wsub,
-                         const std::vector<char>& wpair, const std::vector<rta::Box3>& boxes,
-                         const std::vector<float>& cones, const std::function<int(int)>& leaf_of, size_t sub_base) {
-        float v[kWideRecMt][4];
-        for (int s2 = 0; s2 < 4; ++s2) {
-            const int j = wchild[rta::kWide * w + s2];
-            int code = kNoChild;
-            float box[6] = {0, 0, 0, 0, 0, 0}, cone[4] = {0, 0, 0, -4.f}, mtc[rta::kMtPadF] = {0, 0, 0, 0, 0, 0};
-            if (j >= 0) {
-                const rta::Box3& bx = boxes[j];
-                for (int a = 0; a < 3; ++a) {
-                    box[a] = bx.lo[a];
-                    box[3 + a] = bx.hi[a];
-                }
-                for (int a = 0; a < 4; ++a) cone[a] = cones[4 * j + a];
-                if (!c->cone_cull && cone[3] > rta::kNoPrune) cone[3] = A.mt ? 2.f : -4.f;
-                if (A.mt && boxes.data() == A.lbox.data())
-                    for (int a = 0; a < rta::kMtPadF; ++a) mtc[a] = A.lmt[rta::kMtPadF * j + a];
-                const int sub = wsub[rta::kWide * w + s2];
-                code = sub < 0 ? leaf_of(j) : wide_code(wpair, sub, sub_base);
-            }
-            if (A.mt) {  // per child 16 floats: box, cone, the per-ray padding constants
-                float* blk = &v[0][0] + 16 * s2;
-                for (int a = 0; a < 6; ++a) blk[a] = box[a];
-                for (int a = 0; a < 4; ++a) blk[6 + a] = cone[a];
-                for (int a = 0; a < rta::kMtPadF; ++a) blk[10 + a] = mtc[a];
-            } else {
-                for (int a = 0; a < 6; ++a) v[a][s2] = box[a];
-                v[6][s2] = bits_f(j < 0 ? rta::kConeNever : rta::cone_word(cone[0], cone[1], cone[2], cone[3]));
-            }
-            v[rec - 1][s2] = bits_f(code);
-        }
-        for (int r = 0; r < rec; ++r) ln[rec * at + r] = make_float4(v[r][0], v[r][1], v[r][2], v[r][3]);
-    };
-    {
-        const std::function<int(int)> leaf_of = [&](int j) { return leaf_code(static_cast<size_t>(j)); };
-        rta::parallel_for(static_cast<int>(nw), kPackChunk, [&](int w0, int w1) {
-            for (size_t w = static_cast<size_t>(w0); w < static_cast<size_t>(w1); ++w)
-                emit_wide(w, w, A.wchild, A.wsub, A.wpair, A.lbox, A.lcone, leaf_of, 0);
-        });
+    rta::PackedAccel pk;
+    const bool packed = rta::pack_accel(c->accel, c->host_nodes.data(), c->N, c->cone_cull != 0, pk, &lap);
+    // a refused pack (no accelerator: RT_OK without accel_ok) keeps what it had decided by then
+    if (pk.boxes_finite >= 0) c->boxes_finite = pk.boxes_finite;
+    if (pk.nfew >= 0) c->nfew = pk.nfew;
+    if (pk.nfew >= 0 && pk.use_st) {
+        int rc = alloc_and_copy(c, {host_array(c->titem_ref, pk.titem_ref.data(), pk.titem_ref.size())});
+        if (rc != RT_OK) return rc;
+        c->n_titems = static_cast<int>(pk.titem_ref.size());
+        c->host_titem_ref = std::move(pk.titem_ref);
     }
-    lap("local wide nodes");
-    // Items: with <= 8 distinct reference leaves (few-leaf mode, few_mask) a
-    // local-leaf code kLocal|kLeaf|kItem|start<<6|leaf<<3|count and titems =
-    // the leaves' exact boxes; otherwise kTopLeaf|kItem|item and titems = per
-    // item its leaf's exact box + prim range.
-    std::vector<int> few;
-    if (use_st) {
-        for (int k : T.item_ref)
-            if (std::find(few.begin(), few.end(), k) == few.end()) {
-                few.push_back(k);
-                if (few.size() > 8) break;
-            }
-        if (few.size() > 8) few.clear();
-        for (size_t i = 0; i < T.item_ref.size() && !few.empty(); ++i)
-            if (T.item_count[i] > 7 || T.item_start[i] >= (1 << 22)) few.clear();
-    }
-    c->nfew = static_cast<int>(few.size());
-    auto item_code = [&](int j) {
-        const int i = T.item_of[j];
-        if (few.empty()) return static_cast<int>(kTopLeaf | kItem | static_cast<unsigned>(i));
-        const unsigned f = static_cast<unsigned>(std::find(few.begin(), few.end(), T.item_ref[i]) - few.begin());
-        return static_cast<int>(kLocal | kLeaf | kItem | (static_cast<unsigned>(T.item_start[i]) << 6) | (f << 3) |
-                                static_cast<unsigned>(T.item_count[i]));
-    };
-    std::vector<float4> ti(2 * (use_st ? std::max<size_t>(T.item_ref.size(), 1) : 1));
-    if (use_st) {
-        const std::function<int(int)> item_of = item_code;
-        rta::parallel_for(static_cast<int>(nws), kPackChunk, [&](int w0, int w1) {
-            for (size_t w = static_cast<size_t>(w0); w < static_cast<size_t>(w1); ++w)
-                emit_wide(w, nw + w, T.wchild, T.wsub, T.wpair, T.box, A.st_cone, item_of, nw);
-        });
-        auto put = [&](size_t i, int ref, int start, int count) {
-            const FlatNode& n = c->host_nodes[ref];
-            ti[2 * i] = make_float4(n.boundsMin.x, n.boundsMin.y, n.boundsMin.z, bits_f(start));
-            ti[2 * i + 1] = make_float4(n.boundsMax.x, n.boundsMax.y, n.boundsMax.z, bits_f(count));
-        };
-        if (!few.empty())
-            for (size_t i = 0; i < few.size(); ++i) put(i, few[i], 0, 0);
-        else
-            for (size_t i = 0; i < T.item_ref.size(); ++i) put(i, T.item_ref[i], T.item_start[i], T.item_count[i]);
-        const std::vector<int>& refs = few.empty() ? T.item_ref : few;
-        if (hipMalloc(&c->titem_ref, refs.size() * sizeof(int)) != hipSuccess) return RT_ERR_NO_MEMORY;
-        HIP_TRY(hipMemcpyAsync(c->titem_ref, refs.data(), refs.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        c->n_titems = static_cast<int>(refs.size());
-        c->host_titem_ref = refs;
-    }
-    lap("scene tree nodes, items");
-    // wnodes: per reference inner node both children's exact + content boxes;
-    // tleaf: per reference leaf its plain range and local root code.
-    RawArray<float4> wn(8 * static_cast<size_t>(N));
-    RawArray<int4> tl(static_cast<size_t>(N));
-    auto top_code_of = [&](int k) {
-        return c->host_nodes[k].leftChild == -1 ? static_cast<int>(kTopLeaf | static_cast<unsigned>(k)) : k;
-    };
-    rta::parallel_for(N, kPackChunk, [&](int k0, int k1) {
-        for (int k = k0; k < k1; ++k) {
-            const FlatNode& n = c->host_nodes[k];
-            if (n.leftChild == -1) {
-                const int r = A.local_root[k];
-                const int lr = A.wroot[k] >= 0 ? wide_code(A.wpair, A.wroot[k], 0)
-                                               : (r >= 0 ? leaf_code(static_cast<size_t>(r)) : kNoChild);
-                tl[k] = make_int4(A.plain_start[k], A.plain_count[k], lr, 0);
-                for (int q = 0; q < 8; ++q) wn[8 * static_cast<size_t>(k) + q] = make_float4(0.f, 0.f, 0.f, 0.f);
-                continue;
-            }
-            tl[k] = make_int4(0, 0, kNoChild, 0);
-            const int ch[2] = {n.leftChild, n.rightChild};
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const FlatNode& cn = c->host_nodes[ch[s2]];
-                const rta::Box3& cb = A.content[ch[s2]];
-                float4* q = &wn[8 * static_cast<size_t>(k) + 4 * s2];
-                q[0] = make_float4(cn.boundsMin.x, cn.boundsMin.y, cn.boundsMin.z, s2 == 0 ? bits_f(top_code_of(ch[0])) : 0.f);
-                q[1] = make_float4(cn.boundsMax.x, cn.boundsMax.y, cn.boundsMax.z, s2 == 0 ? bits_f(top_code_of(ch[1])) : 0.f);
-                q[2] = make_float4(cb.lo[0], cb.lo[1], cb.lo[2], bits_f(A.flags[ch[s2]] & 8));
-                q[3] = make_float4(cb.hi[0], cb.hi[1], cb.hi[2], 0.f);
-            }
-        }
-    });
-    lap("wnodes, tleaf");
-    if (!codes_ok.load()) return RT_OK;
-    for (size_t i = 0; i < P; ++i)  // PrimRec::st = seq << 2 | type
-        if (A.prim_seq[i] < 0 || A.prim_seq[i] >= (1 << 29)) return RT_OK;
-    std::vector<int> ps(2 * (P ? P : 1));
-    for (size_t i = 0; i < P; ++i) {
-        ps[i] = A.prim_shape[i];
-        ps[P + i] = A.prim_seq[i];
-    }
-    lap("prim lists");
-    if (hipMalloc(&c->anodes, an.size() * sizeof(float4)) != hipSuccess ||
-        hipMalloc(&c->lnodes, ln.size() * sizeof(float4)) != hipSuccess ||
-        hipMalloc(&c->wnodes, wn.size() * sizeof(float4)) != hipSuccess ||
-        hipMalloc(&c->tleaf, tl.size() * sizeof(int4)) != hipSuccess ||
-        hipMalloc(&c->titems, ti.size() * sizeof(float4)) != hipSuccess ||
-        hipMalloc(&c->prims, 4 * (P ? P : 1) * sizeof(float4)) != hipSuccess ||
-        hipMalloc(&c->prim_idx_dev, ps.size() * sizeof(int)) != hipSuccess)
-        return RT_ERR_NO_MEMORY;
-    lap("hipMalloc");
-    HIP_TRY(hipMemcpyAsync(c->anodes, an.data(), an.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->lnodes, ln.data(), ln.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->wnodes, wn.data(), wn.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->tleaf, tl.data(), tl.size() * sizeof(int4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->titems, ti.data(), ti.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->prim_idx_dev, ps.data(), ps.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (!packed) return RT_OK;
+    const size_t P = c->accel.prim_shape.size();
+    int rc = alloc_and_copy(c,
+                            {host_array(c->anodes, pk.an.data(), pk.an.size()), host_array(c->lnodes, pk.ln.data(), pk.ln.size()),
+                             host_array(c->wnodes, pk.wn.data(), pk.wn.size()), host_array(c->tleaf, pk.tl.data(), pk.tl.size()),
+                             host_array(c->titems, pk.ti.data(), pk.ti.size()),
+                             host_array(c->prims, static_cast<const float4*>(nullptr), 4 * (P ? P : 1)),
+                             host_array(c->prim_idx_dev, pk.ps.data(), pk.ps.size())},
+                            &lap);
+    if (rc != RT_OK) return rc;
     if (P > 0)
         hipLaunchKernelGGL(k_pack_prims, dim3((P + 255) / 256), dim3(256), 0, c->stream, c->geo_lin, c->prim_idx_dev,
                            c->prim_idx_dev + P, static_cast<int>(P), c->prims);
     HIP_TRY(hipGetLastError());
     lap("copies issued");
-    HIP_TRY(sync_stream(c));  // the host vectors die here
+    HIP_TRY(sync_stream(c));  // the packed arrays die with pk
     lap("copies + pack done");
-    c->st_root = use_st ? wide_code(T.wpair, T.wroot, nw) : kNoChild;
+    c->st_root = pk.st_root;
     c->accel_ok = true;
-    c->record_bytes = (an.size() + ln.size() + wn.size() + tl.size() + ti.size() + 4 * P + 2 * static_cast<size_t>(c->S)) *
-                      sizeof(float4);
+    c->record_bytes = (pk.an.size() + pk.ln.size() + pk.wn.size() + pk.tl.size() + pk.ti.size() + 4 * P +
+                       2 * static_cast<size_t>(c->S)) * sizeof(float4);
     return RT_OK;
 }
 
@@ -4229,17 +4042,9 @@ int sync_host_nodes(rt_ctx* c) {
 // items' exact boxes still gate). Idempotent; reset by every accelerator build.
 int open_inf_slots(rt_ctx* c) {
     if (c->inf_open || !c->accel_ok) return RT_OK;
-    const rta::AccelHost& A = c->accel;
-    const rta::SceneTree& T = A.st;
     c->inf_open = true;
-    if (T.wroot < 0) return RT_OK;
-    const size_t nw = A.wchild.size() / rta::kWide;
-    std::vector<int> slots;
-    for (size_t q = 0; q < T.wchild.size(); ++q) {
-        const int j = T.wchild[q];
-        if (j >= 0 && A.st_cone[4 * static_cast<size_t>(j) + 3] <= rta::kNoPrune)
-            slots.push_back(static_cast<int>(4 * nw + q));
-    }
+    if (c->accel.st.wroot < 0) return RT_OK;
+    const std::vector<int> slots = rta::noprune_slots(c->accel);
     hipFree(c->anim_inf_slots);
     c->anim_inf_slots = nullptr;
     c->n_inf_slots = static_cast<int>(slots.size());
@@ -4262,315 +4067,55 @@ int prepare_animation(rt_ctx* c) {
     const int n = static_cast<int>(c->refit_ids.size());
     c->anim = AnimMaps{};
     c->n_direct_slot_reads = 0;
-    c->refit_of.assign(c->S, -1);
-    for (int i = 0; i < n; ++i) c->refit_of[c->refit_ids[i]] = i;
-    c->entry_root.clear();
-    if (n == 0) return RT_OK;
-    const int N = c->N;
-    const std::vector<int>& which = c->refit_of;  // shape -> refit entry
-    const rta::AccelHost& A = c->accel;
-    c->anim_cls.assign(n, rta::UNBOUNDED);
-    for (int i = 0; i < n; ++i) {
-        rta::Box3 b;
-        c->anim_cls[i] = rta::classify(c->anim_base[i], b, A.origin_lim, A.mt);
-    }
-    // reference nodes listing each shape: the leaves that list it and every node above
-    // (CSR: a vector per node took ~6 ms of a config-5 setup)
-    std::vector<int> poff(static_cast<size_t>(N) + 1, 0), plist;
-    for (int k = 0; k < N; ++k) {
-        const FlatNode& nd = c->host_nodes[k];
-        if (nd.leftChild != -1) {
-            ++poff[nd.leftChild + 1];
-            if (nd.rightChild != nd.leftChild) ++poff[nd.rightChild + 1];
-        }
-    }
-    for (int k = 0; k < N; ++k) poff[k + 1] += poff[k];
-    plist.resize(poff[N]);
+    rta::RefitPlan pl;
+    const rta::RefitState state{c->refit_of, c->anim_cls, c->entry_root};
     {
-        std::vector<int> fill(poff.begin(), poff.end() - 1);
-        for (int k = 0; k < N; ++k) {
-            const FlatNode& nd = c->host_nodes[k];
-            if (nd.leftChild != -1) {
-                plist[fill[nd.leftChild]++] = k;
-                if (nd.rightChild != nd.leftChild) plist[fill[nd.rightChild]++] = k;
-            }
+        rta::RefitSlots sl;  // the slot arrays die before the lists are built
+        const int planned = rta::plan_refit_slots(c->accel, c->accel_ok, c->host_nodes.data(), c->N, c->host_idx.data(), c->S,
+                                                  c->refit_ids, c->anim_base, c->host_shapes.data(),
+                                                  rta::ShapeCache{c->accel.shape_cls, c->accel.shape_box, c->shape_moved}, state,
+                                                  pl, sl, &lap);
+        if (n == 0 || planned != RT_OK) return planned;
+        if (pl.slots) {
+            c->dirty_max = pl.dirty_max;
+            c->dirty_sum = pl.dirty_sum;
+            c->n_big = pl.n_big;
+            hipFree(c->pbox);
+            hipFree(c->refit_dirty);
+            hipFree(c->refit_static);
+            hipFree(c->refit_list);
+            c->pbox = nullptr;
+            c->refit_dirty = nullptr;
+            c->refit_static = nullptr;
+            c->refit_list = nullptr;
+            c->n_dirty = 0;
+            int rc = alloc_and_copy(c, {host_array(c->pbox, sl.pb.data(), sl.pb.size()),
+                                        host_array(c->refit_dirty, sl.work.data(), sl.work.size()),
+                                        host_array(c->refit_static, sl.st.data(), sl.st.size()),
+                                        host_array(c->refit_list, sl.dl.data(), sl.dl.size())});
+            if (rc != RT_OK) return rc;
+            c->n_dirty = pl.n_dirty;
+            c->n_direct_slot_reads = pl.n_direct_slot_reads;
+            rc = open_inf_slots(c);
+            if (rc != RT_OK) return rc;
         }
-    }
-    std::vector<std::vector<int>> nodes_of(n), slots_of(n), prims_of(n), wpos_of(n);
-    std::vector<int> stamp(N, -1);
-    for (int k = 0; k < N; ++k) {
-        const FlatNode& nd = c->host_nodes[k];
-        if (nd.leftChild != -1) continue;
-        for (int j = nd.startShapeIdx; j < nd.startShapeIdx + nd.numShapes; ++j) {
-            const int i = which[c->host_idx[j]];
-            if (i < 0) continue;
-            slots_of[i].push_back(j);
-            nodes_of[i].push_back(k);
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        std::vector<int>& L = nodes_of[i];
-        std::vector<int> todo;
-        for (int k : L)
-            if (stamp[k] != i) {
-                stamp[k] = i;
-                todo.push_back(k);
-            }
-        L.clear();
-        while (!todo.empty()) {
-            const int k = todo.back();
-            todo.pop_back();
-            L.push_back(k);
-            for (int q = poff[k]; q < poff[k + 1]; ++q)
-                if (const int p = plist[q]; stamp[p] != i) {
-                    stamp[p] = i;
-                    todo.push_back(p);
-                }
-        }
-        std::sort(L.begin(), L.end());
-    }
-    lap("nodes_of");
-    c->entry_root.assign(n, 0);
-    for (int i = 0; i < n; ++i) c->entry_root[i] = std::binary_search(nodes_of[i].begin(), nodes_of[i].end(), N - 1);
-    if (c->accel_ok) {
-        const size_t P = A.prim_shape.size(), M = A.lbox.size();
-        std::vector<int> lleaf(P, -1), lparent(M, -1), wpos(M, -1);
-        for (size_t j = 0; j < M; ++j) {
-            if (A.la[j] < 0) {
-                const int st = -A.la[j] - 1;
-                for (int q = 0; q < A.lb[j]; ++q) lleaf[st + q] = static_cast<int>(j);
-            } else {
-                lparent[A.la[j]] = static_cast<int>(j);
-                lparent[A.lb[j] & 0x3fffffff] = static_cast<int>(j);
-            }
-        }
-        for (size_t q = 0; q < A.wchild.size(); ++q)
-            if (A.wchild[q] >= 0) wpos[A.wchild[q]] = static_cast<int>(q);
-        std::vector<int> wstamp(M, -1);
-        std::vector<char> dirty(M, 0);
-        for (size_t p = 0; p < P; ++p) {
-            const int i = which[A.prim_shape[p]];
-            if (i < 0) continue;
-            prims_of[i].push_back(static_cast<int>(p));
-            for (int j = lleaf[p]; j >= 0; j = lparent[j])
-                if (wpos[j] >= 0 && wstamp[j] != i) {
-                    wstamp[j] = i;
-                    wpos_of[i].push_back(wpos[j]);
-                    dirty[j] = 1;
-                }
-        }
-    lap("local maps");
-        // prim range of every local subtree (contiguous: LocalBuilder emits a subtree's prims together)
-        std::vector<int> first, end;
-        if (!rta::local_prim_ranges(A, first, end)) return RT_ERR_BVH;
-        std::vector<int4> work;
-        for (size_t j = 0; j < M; ++j)
-            if (dirty[j]) work.push_back(make_int4(wpos[j], first[j], end[j], 0));
-        // The scene tree (accel.h SceneTree), refit like the local trees: its wide
-        // nodes follow the local ones in lnodes (global slot 4*nw + q), a subtree's
-        // prims are contiguous. Its unbounded part (kNoPrune: boxes are the padded
-        // reference-leaf boxes, which grow) goes infinite while the set is animated;
-        // the items' exact boxes follow the grown leaves (k_refit).
-    lap("local ranges");
-        const rta::SceneTree& T = A.st;
-        if (T.wroot >= 0) {
-            const size_t nw = A.wchild.size() / rta::kWide, Ms = T.box.size();
-            std::vector<int> sparent(Ms, -1), swpos(Ms, -1), sfirst, send, sleaf(P, -1);
-            for (size_t j = 0; j < Ms; ++j) {
-                if (T.a[j] < 0) {
-                    const int st = -T.a[j] - 1;
-                    for (int q = 0; q < T.b[j]; ++q) sleaf[st + q] = static_cast<int>(j);
-                } else {
-                    sparent[T.a[j]] = static_cast<int>(j);
-                    sparent[T.b[j] & 0x3fffffff] = static_cast<int>(j);
-                }
-            }
-            rta::scene_prim_ranges(T, sfirst, send);
-            for (size_t q = 0; q < T.wchild.size(); ++q)
-                if (T.wchild[q] >= 0) swpos[T.wchild[q]] = static_cast<int>(4 * nw + q);
-            auto noprune = [&](int j) { return A.st_cone[4 * static_cast<size_t>(j) + 3] <= rta::kNoPrune; };
-            std::vector<int> sstamp(Ms, -1);
-            std::vector<char> sdirty(Ms, 0);
-            for (size_t p = 0; p < P; ++p) {
-                const int i = which[A.prim_shape[p]];
-                if (i < 0 || sleaf[p] < 0) continue;
-                for (int j = sleaf[p]; j >= 0; j = sparent[j])
-                    if (swpos[j] >= 0 && !noprune(j) && sstamp[j] != i) {
-                        sstamp[j] = i;
-                        wpos_of[i].push_back(swpos[j]);
-                        sdirty[j] = 1;
-                    }
-            }
-            for (size_t j = 0; j < Ms; ++j)
-                if (sdirty[j]) work.push_back(make_int4(swpos[j], sfirst[j], send[j], 0));
-        }
-    lap("scene tree maps");
-        std::vector<float4> pb(2 * (P ? P : 1), make_float4(INFINITY, INFINITY, INFINITY, 0.f));
-        // per shape its class and box as last classified (the build's, or here for shapes
-        // written since: a host rewriting a different 1 % of config 5 every frame had
-        // every shape it ever wrote classified again at each change of the set, 11 ms)
-        const bool cached = A.shape_cls.size() == static_cast<size_t>(c->S) && c->shape_moved.size() == A.shape_cls.size();
-        for (size_t p = 0; p < P; ++p) {
-            rta::Box3 b;
-            const int sh = A.prim_shape[p];
-            int cls;
-            if (cached && !c->shape_moved[sh]) {
-                cls = A.shape_cls[sh];
-                b = A.shape_box[sh];
-            } else {
-                cls = rta::classify(c->host_shapes[sh], b, A.origin_lim, A.mt);
-                if (cached) {
-                    c->accel.shape_cls[sh] = cls;
-                    c->accel.shape_box[sh] = b;
-                    c->shape_moved[sh] = 0;
-                }
-            }
-            if (cls != rta::BOUNDED) {
-                pb[2 * p + 1] = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f);
-                continue;
-            }
-            pb[2 * p] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f);
-            pb[2 * p + 1] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
-        }
-    lap("prim boxes (classify)");
-        // per dirty slot: the box of its prims outside the refit set (they never move
-        // while this set stands) and the list of those in it, which k_refit unions per frame
-        c->dirty_max = c->dirty_sum = 0;
-        // slots whose refit list takes a wave more than one step (kBigList) first, one
-        // workgroup each; the rest kRefitWaves to a workgroup, one wave each (k_refit)
-        {
-            std::vector<char> big(work.size(), 0);
-            for (size_t q = 0; q < work.size(); ++q) {
-                int n_ref = 0;
-                for (int p = work[q].y; p < work[q].z; ++p) n_ref += which[A.prim_shape[p]] >= 0;
-                big[q] = n_ref > kBigList;
-            }
-            std::vector<int4> ord;
-            for (int pass = 1; pass >= 0; --pass)
-                for (size_t q = 0; q < work.size(); ++q)
-                    if (big[q] == pass) ord.push_back(work[q]);
-            c->n_big = static_cast<int>(std::count(big.begin(), big.end(), 1));
-            work.swap(ord);
-        }
-        std::vector<float4> st(2 * (work.empty() ? 1 : work.size()));
-        std::vector<int> dl;
-        for (size_t q = 0; q < work.size(); ++q) {
-            int4& w4 = work[q];
-            c->dirty_max = std::max(c->dirty_max, w4.z - w4.y);
-            c->dirty_sum += w4.z - w4.y;
-            w4.w = static_cast<int>(dl.size());
-            float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-            for (int p = w4.y; p < w4.z; ++p) {
-                if (which[A.prim_shape[p]] >= 0) {
-                    dl.push_back(p);
-                    continue;
-                }
-                const float4 a = pb[2 * static_cast<size_t>(p)], b = pb[2 * static_cast<size_t>(p) + 1];
-                lo[0] = std::min(lo[0], a.x), lo[1] = std::min(lo[1], a.y), lo[2] = std::min(lo[2], a.z);
-                hi[0] = std::max(hi[0], b.x), hi[1] = std::max(hi[1], b.y), hi[2] = std::max(hi[2], b.z);
-            }
-            st[2 * q] = make_float4(lo[0], lo[1], lo[2], 0.f);
-            st[2 * q + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
-        }
-    lap("slot static boxes");
-        const int nw = static_cast<int>(work.size());
-        work.push_back(make_int4(0, 0, 0, static_cast<int>(dl.size())));  // the end of the last list
-        if (dl.empty()) dl.push_back(0);
-        hipFree(c->pbox);
-        hipFree(c->refit_dirty);
-        hipFree(c->refit_static);
-        hipFree(c->refit_list);
-        c->pbox = nullptr;
-        c->refit_dirty = nullptr;
-        c->refit_static = nullptr;
-        c->refit_list = nullptr;
-        c->n_dirty = 0;
-        if (hipMalloc(&c->pbox, pb.size() * sizeof(float4)) != hipSuccess ||
-            hipMalloc(&c->refit_dirty, work.size() * sizeof(int4)) != hipSuccess ||
-            hipMalloc(&c->refit_static, st.size() * sizeof(float4)) != hipSuccess ||
-            hipMalloc(&c->refit_list, dl.size() * sizeof(int)) != hipSuccess)
-            return RT_ERR_NO_MEMORY;
-        HIP_TRY(hipMemcpyAsync(c->pbox, pb.data(), pb.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->refit_dirty, work.data(), work.size() * sizeof(int4), hipMemcpyHostToDevice,
-                               c->stream));
-        HIP_TRY(hipMemcpyAsync(c->refit_static, st.data(), st.size() * sizeof(float4), hipMemcpyHostToDevice,
-                               c->stream));
-        HIP_TRY(hipMemcpyAsync(c->refit_list, dl.data(), dl.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        c->n_dirty = nw;
-        c->n_direct_slot_reads = static_cast<long long>(work.back().w);  // the slots' refit prims
-        const int rc = open_inf_slots(c);
-        if (rc != RT_OK) return rc;
     }
     lap("slot uploads");
-    // one int allocation: ids, then (offsets, list) x 4
-    std::vector<int> buf(c->refit_ids);
-    auto append = [&](const std::vector<std::vector<int>>& lists, size_t& off_at, size_t& list_at) {
-        off_at = buf.size();
-        int run = 0;
-        buf.push_back(0);
-        for (const auto& l : lists) buf.push_back(run += static_cast<int>(l.size()));
-        list_at = buf.size();
-        for (const auto& l : lists) buf.insert(buf.end(), l.begin(), l.end());
-    };
-    // per reference node, the animated shapes it lists (k_refit's node role)
-    std::vector<int> node_ids;
-    std::vector<std::vector<int>> lists_of;
-    {
-        std::vector<int> slot(N, -1);
-        for (int i = 0; i < n; ++i)
-            for (int k : nodes_of[i]) {
-                if (slot[k] < 0) {
-                    slot[k] = static_cast<int>(node_ids.size());
-                    node_ids.push_back(k);
-                    lists_of.emplace_back();
-                }
-                lists_of[slot[k]].push_back(i);
-            }
-    }
-    // per grown node, where its box is copied (k_refit writes them through): the
-    // wnodes child slots of its parent(s) and the scene-tree items it gates
-    std::vector<std::vector<int>> wn_of(node_ids.size()), items_of(node_ids.size());
-    {
-        std::vector<int> slot(N, -1);
-        for (size_t j = 0; j < node_ids.size(); ++j) slot[node_ids[j]] = static_cast<int>(j);
-        for (int p = 0; p < N; ++p) {
-            const FlatNode& nd = c->host_nodes[p];
-            if (nd.leftChild == -1) continue;
-            if (slot[nd.leftChild] >= 0) wn_of[slot[nd.leftChild]].push_back(2 * p);
-            if (slot[nd.rightChild] >= 0) wn_of[slot[nd.rightChild]].push_back(2 * p + 1);
-        }
-        if (c->accel_ok && c->titems)
-            for (size_t i = 0; i < c->host_titem_ref.size(); ++i) {
-                const int k = c->host_titem_ref[i];
-                if (k >= 0 && k < N && slot[k] >= 0) items_of[slot[k]].push_back(static_cast<int>(i));
-            }
-    }
-    size_t o[12];
-    append(slots_of, o[0], o[1]);
-    append(prims_of, o[2], o[3]);
-    append(wpos_of, o[4], o[5]);
-    append(lists_of, o[6], o[7]);
-    c->direct_reads = n + c->n_direct_slot_reads;
-    for (const auto& l : lists_of) c->direct_reads += static_cast<long long>(l.size());
-    append(wn_of, o[8], o[9]);
-    append(items_of, o[10], o[11]);
-    const size_t o_ids = buf.size();
-    buf.insert(buf.end(), node_ids.begin(), node_ids.end());
-    const size_t o_cls = buf.size();  // per entry: the class the accelerator was built with
-    buf.insert(buf.end(), c->anim_cls.begin(), c->anim_cls.end());
-    const size_t o_pe = buf.size();   // per accelerator prim: its shape's refit entry (-1: none)
-    for (size_t p = 0; p < (c->accel_ok ? A.prim_shape.size() : 0); ++p) buf.push_back(which[A.prim_shape[p]]);
+    static const std::vector<int> no_items;
+    rta::plan_refit_lists(c->accel, c->accel_ok, c->host_nodes.data(), c->N, c->refit_ids,
+                          c->accel_ok && c->titems ? c->host_titem_ref : no_items, state, pl);
+    c->direct_reads = pl.direct_reads;
     lap("node lists");
-    int rc = ensure_staging(c->anim_maps, c->anim_maps_cap, buf.size());
+    int rc = ensure_staging(c->anim_maps, c->anim_maps_cap, pl.buf.size());
     if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->anim_maps, buf.data(), buf.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(sync_stream(c));
+    HIP_TRY(hipMemcpyAsync(c->anim_maps, pl.buf.data(), pl.buf.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(sync_stream(c));  // the plan's arrays die with pl
     lap("maps upload + sync");
     const int* d = c->anim_maps;
-    c->anim = AnimMaps{d,        d + o[0], d + o[1],  d + o[2],  d + o[3], d + o[4], d + o[5], d + o_ids,
-                       d + o[6], d + o[7], d + o[8], d + o[9], d + o[10], d + o[11], d + o_cls, d + o_pe,
-                       n,
-                       static_cast<int>(node_ids.size())};
+    const rta::RefitOffsets& o = pl.o;
+    c->anim = AnimMaps{d + o.ids,       d + o.slot_off,  d + o.slot_list, d + o.prim_off, d + o.prim_list, d + o.wpos_off,
+                       d + o.wpos_list, d + o.node_ids,  d + o.node_off,  d + o.node_list, d + o.wn_off,   d + o.wn_list,
+                       d + o.item_off,  d + o.item_list, d + o.ecls,      d + o.prim_entry, n,              pl.n_nodes};
     return ensure_staging(c->anim_sbox, c->anim_sbox_cap, 4 * static_cast<size_t>(n));
 }
 

@@ -1,6 +1,7 @@
 // fuzz_host.cpp — TEST HARNESS: drives the product's host code (librtscene's
 // scene.cpp: OBJ parser, builder, serialisers, image dump; accel.cpp: the
-// accelerator build that rt_upload_scene runs on the host) over malformed and
+// accelerator build that rt_upload_scene runs on the host; accel_pack.h and
+// refit_plan.h: its packed device layout and the refit's maps) over malformed and
 // randomly mutated inputs. tests/test_sanitize.py compiles it together with
 // those two sources under AddressSanitizer + UndefinedBehaviorSanitizer
 // (-fno-sanitize-recover: the first finding aborts) and runs it on the CPU.
@@ -20,6 +21,8 @@
 
 #include "../../include/rt_scene.h"
 #include "../../opengl-ray-tracer_amd/csrc/accel.h"
+#include "../../opengl-ray-tracer_amd/csrc/accel_pack.h"
+#include "../../opengl-ray-tracer_amd/csrc/refit_plan.h"
 
 namespace {
 
@@ -74,7 +77,7 @@ std::string mutate(const std::string& s) {
     return m;
 }
 
-int g_loaded = 0, g_rejected = 0, g_built = 0;
+int g_loaded = 0, g_rejected = 0, g_built = 0, g_planned = 0;
 
 // rt_upload_scene's host half: serialise the reference tree, then build the accelerator over it.
 void build_everything(rts_scene* s, int max_depth) {
@@ -91,7 +94,28 @@ void build_everything(rts_scene* s, int max_depth) {
     rts_bvh_stats(s, &leaves, &max_leaf, &depth, &stack);
     if (N > 0) {
         rta::AccelHost A;
-        if (rta::build_accel(shapes.data(), S, nodes.data(), N, idx.data(), I, 8, 64, A)) ++g_built;
+        if (!rta::build_accel(shapes.data(), S, nodes.data(), N, idx.data(), I, rta::kLeafScan, rta::kMaxStack, A)) return;
+        ++g_built;
+        // upload_built_accel's and prepare_animation's host halves: the packed device layout,
+        // then the refit's maps for every third shape
+        rta::PackedAccel pk;
+        const bool packed = rta::pack_accel(A, nodes.data(), N, (rnd() & 1) != 0, pk);
+        std::vector<int> ids;
+        std::vector<FlatShape> base;
+        for (int i = 0; i < S && ids.size() < 64; i += 3) {
+            ids.push_back(i);
+            base.push_back(shapes[i]);
+        }
+        std::vector<char> moved(S, 0);
+        for (int id : ids) moved[id] = 1;
+        rta::RefitPlan pl;
+        rta::RefitSlots sl;
+        std::vector<int> refit_of, anim_cls;
+        std::vector<char> entry_root;
+        rta::plan_refit(A, packed, nodes.data(), N, idx.data(), S, ids, base, shapes.data(),
+                        rta::ShapeCache{A.shape_cls, A.shape_box, moved}, rta::RefitState{refit_of, anim_cls, entry_root},
+                        pk.titem_ref, pl, sl);
+        g_planned += pl.slots ? 1 : 0;
     }
 }
 
@@ -176,7 +200,7 @@ int main(int argc, char** argv) {
     bad += rts_write_image("/tmp/fuzz_host.ppm", img.data(), 0, 5, 7 * 16, RTS_IMAGE_PPM) == 0;
     std::remove("/tmp/fuzz_host.ppm");
     std::remove("/tmp/fuzz_host.pfm");
-    std::printf("loaded %d, rejected %d, accelerators built %d, image checks failed %d\n", g_loaded, g_rejected,
-                g_built, bad);
+    std::printf("loaded %d, rejected %d, accelerators built %d, refits planned %d, image checks failed %d\n", g_loaded,
+                g_rejected, g_built, g_planned, bad);
     return bad ? 1 : 0;
 }

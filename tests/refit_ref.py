@@ -20,9 +20,11 @@ grown_nodes(fs, ids, frames) gives the node records a group's frame slot must ho
 frames given to the group (updateBVH once per frame), and shifted() builds frames that each leave
 a trace in them (tests/test_group_refit_cpu.py, tests/test_gpu_group_refit_state.py).
 
-Only four product functions are used as they are (tests/native/refit_ref.cpp): classify,
-classify_mt_tight's constants, cone_culls_q with ray_consts, and the cone word's fields.
-Everything else is numpy in float64 or exact float32 min / max.
+Only four product functions are used as they are by check() (tests/native/refit_ref.cpp):
+classify, classify_mt_tight's constants, cone_culls_q with ray_consts, and the cone word's
+fields. Everything else is numpy in float64 or exact float32 min / max. A fifth, the packer
+(accel_pack.h pack_accel), is used only by host_dump(): the dump of a fresh build without a GPU
+is what the renderer would upload, code words included; check() never calls it.
 """
 import ctypes as C
 import os

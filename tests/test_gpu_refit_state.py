@@ -180,6 +180,27 @@ def test_layouts(ctx, fresh, run_factory):
     assert 0 < d2["nfew"] == d2["n_titems"] <= 8
 
 
+def test_upload_copies_the_packed_arrays():
+    """A fresh upload of soup6 and of soup2 holds the host packer's arrays (accel_pack.h
+    pack_accel, through refit_ref.host_dump) byte for byte, in a context and in its Moller-
+    Trumbore one: anodes, wnodes, titems, lnodes with their code words, the titems' leaves, and
+    the info words. (A context of its own: the others keep no Moller-Trumbore sub-context.)"""
+    c = rtamd.ComputeShader(0)
+    try:
+        for name in ("soup6", "soup2"):
+            fs = scene(name)
+            c.upload(fs)
+            c.set_params(W, H, 3, True, False, True)
+            c.render(W, H)  # creates the Moller-Trumbore sub-context
+            for w, mt in (("own", 0), ("mtc", 1)):
+                d, h = c.debug_accel_dump(w), rr.host_dump(fs, mt)
+                assert d["built"] == 1 and d["mt"] == mt
+                for sec in ("anodes", "wnodes", "titems", "lnodes", "titem_ref", "info"):
+                    assert d[sec].shape == h[sec].shape and d[sec].tobytes() == h[sec].tobytes(), (name, w, sec)
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 300, 1100])
 @pytest.mark.parametrize("name", ["soup6", "soup2"])

@@ -2,7 +2,8 @@
 
 tests/native/fuzz_host.cpp drives the product's host sources (scene.cpp: the
 OBJ parser, the reference builder, serialisers and image dump; accel.cpp: the
-accelerator build that rt_upload_scene runs) over malformed and mutated OBJ
+accelerator build that rt_upload_scene runs; accel_pack.h pack_accel and refit_plan.h
+plan_refit: what it uploads and the refit's maps) over malformed and mutated OBJ
 text, degenerate shape soups (NaN/inf coordinates, slivers, +-Y walls) and the
 benchmark scenes. Built with -fsanitize=address,undefined,float-cast-overflow
 and -fno-sanitize-recover: any finding aborts the run. (The HIP device code is
