@@ -1163,8 +1163,13 @@ static void build_scene_tree(const FlatShape* shapes, const FlatNode* nodes, int
             ub.clear();
             for (int i = 0; i < std::max(0, nd.numShapes); ++i) {
                 const int si = idx[nd.startShapeIdx + i];
-                if (scls[si] == NEVER) continue;
-                if (scls[si] == UNBOUNDED) ub.push_back({si, seq_base[k] + i});
+                // NEVER (an unknown type) goes with UNBOUNDED: a prim whose packed test cannot
+                // hit (pack_prim), in an atom that is always entered. A refit may give the shape
+                // a known type: k_refit then rewrites that prim, and as for any shape that was
+                // not BOUNDED at the build it grows no box above it (entry_cbox), so only an
+                // atom entered whatever its box says keeps that frame exact. Left out of the
+                // build, the shape was missing from the frames until the rebuild landed.
+                if (scls[si] != BOUNDED) ub.push_back({si, seq_base[k] + i});
                 else bnd.push_back(i);
             }
             // an atom of n (shape, seq) pairs starting at p
@@ -1442,8 +1447,13 @@ bool build_accel(const FlatShape* shapes, int S, const FlatNode* nodes, int N, c
             for (int i = 0; i < std::max(0, nd.numShapes); ++i) {
                 const int si = idx[nd.startShapeIdx + i];
                 const int seq = seq_base[k] + i;
-                if (scls[si] == NEVER) continue;
-                if (scls[si] == UNBOUNDED) {
+                // UNBOUNDED, and NEVER (an unknown type): an always-tested prim; NEVER's packed test
+                // cannot hit (pack_prim). Both clear the leaf's content cull (unb): a refit that
+                // makes such a shape BOUNDED, or gives it a known type, rewrites its prim but
+                // grows no box for it (k_refit's entry_cbox: never bounded since the build), so the
+                // content box would not hold it. The price is a leaf entered by rays that miss
+                // its content, in scenes that carry records of unknown type.
+                if (scls[si] != BOUNDED) {
                     L.plain.push_back({si, seq});
                     unb = true;
                     continue;

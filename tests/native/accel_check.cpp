@@ -104,6 +104,16 @@ bool padded(const rta::RayC& c, const rta::Box3& b, float l) {
 
 extern "C" {
 
+// accel_bound.h's class of each record (0 UNBOUNDED, 1 BOUNDED, 2 NEVER): what the build sorts
+// the shapes by, and what k_refit compares a moved record's class with. The class does not
+// depend on origin_lim (only the box does): 0 here.
+void accel_classes(const FlatShape* shapes, int S, int mt, int* out_cls) {
+    for (int i = 0; i < S; ++i) {
+        rta::Box3 b;
+        out_cls[i] = rta::classify(shapes[i], b, 0.0, mt != 0);
+    }
+}
+
 // FNV-1a over every field of the accelerator built for the scene (0 if it cannot be
 // built): equal hashes mean the same accelerator.
 unsigned long long accel_hash(const FlatShape* shapes, int S, const FlatNode* nodes, int N, const int* idx, int I,

@@ -26,6 +26,7 @@ import torch
 
 import oracle
 import rtamd
+from frame_check import close_to_oracle
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -42,10 +43,7 @@ def ctx():
 
 
 def check(img, ref, what):
-    diff = np.abs(img.astype(np.float64) - ref.astype(np.float64))
-    bad = int((diff > TOL).any(axis=-1).sum())
-    assert np.isfinite(img).all() == np.isfinite(ref).all(), what
-    assert bad == 0, f"{what}: {bad} pixels over {TOL}, max diff {np.nanmax(diff):.3g}"
+    close_to_oracle(img, ref, TOL, what)
 
 
 def render(ctx, fs, W, H, mb, kernel=rtamd.KERNEL_AUTO, y0=0, rows=None):

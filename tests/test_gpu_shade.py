@@ -17,6 +17,7 @@ import oracle
 import rtamd
 import shade_ref as sr
 import trace_rays as tr
+from frame_check import close_to_oracle
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -98,9 +99,7 @@ def as_rgba(raw):
 
 
 def near_oracle(px, ref, what):
-    diff = np.abs(px.astype(np.float64) - ref.reshape(-1, 4).astype(np.float64))
-    bad = int((diff > TOL).any(axis=-1).sum())
-    assert bad == 0, f"{what}: {bad} pixels over {TOL} from the oracle, max {np.nanmax(diff):.3g}"
+    close_to_oracle(px, ref.reshape(-1, 4), TOL, what)
 
 
 @pytest.mark.parametrize("size", [(W0, H0)] + list(gr.EDGE_SIZES), ids=lambda s: "%dx%d" % s)

@@ -19,6 +19,7 @@ import torch
 import bench
 import oracle
 import rtamd
+from frame_check import close_to_oracle
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -44,10 +45,7 @@ def fresh():
 
 
 def check(img, ref, what):
-    diff = np.abs(img.astype(np.float64) - ref.astype(np.float64))
-    bad = int((diff > TOL).any(axis=-1).sum())
-    assert np.isfinite(img).all() == np.isfinite(ref).all(), what
-    assert bad == 0, f"{what}: {bad} pixels over {TOL}, max diff {np.nanmax(diff):.3g}"
+    close_to_oracle(img, ref, TOL, what)
 
 
 def same(a, b, what):

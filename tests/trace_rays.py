@@ -20,8 +20,12 @@ SCENES = ("cfg2", "cfg3", "cfg5", "soup1")
 
 @functools.lru_cache(maxsize=None)
 def scene(name):
-    """cfg2 / cfg3 / cfg5: the generator's scenes at 96x54; soup1: the adversarial soup."""
-    if name.startswith("soup"):
+    """cfg2 / cfg3 / cfg5: the generator's scenes at 96x54; soup1: the adversarial soup;
+    degenerate/<family>/<seed>/<depth>: a scene of tests/degenerate_scenes.py."""
+    if name.startswith("degenerate/"):
+        import degenerate_scenes as dg
+        fs = dg.scene_of_key(name)
+    elif name.startswith("soup"):
         import test_gpu_parity as tg
         fs = tg._soup(int(name[4:]))
     else:
