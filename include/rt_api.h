@@ -53,8 +53,11 @@ enum rt_kernel {
     RT_KERNEL_AUTO = 0,      /* pick the fastest for the uploaded scene               */
     RT_KERNEL_LANE = 1,      /* one ray per lane, per-lane LDS stack (reference walk) */
     RT_KERNEL_PACKET = 2,    /* wave64 packet walk, wave-uniform stack + active mask  */
-    RT_KERNEL_ACCEL = 3      /* packet walk + exact-result leaf accelerator (default  */
+    RT_KERNEL_ACCEL = 3,     /* packet walk + exact-result leaf accelerator (default  */
                              /* for BVH + barycentric; falls back to PACKET otherwise)*/
+    RT_KERNEL_LIGHTS = 4     /* reported only (rt_accel_info::last_kernel): the frame */
+                             /* of two or more lights over the accelerator            */
+                             /* (rt_set_lights); rt_set_kernel does not take it       */
 };
 
 /* Accelerator statistics of the uploaded scene (rt_accel_info). */
@@ -155,6 +158,56 @@ int rt_read_nodes(struct rt_ctx* ctx, FlatNode* nodes, int num_nodes);
 /* SSBO 2 and 1 (src/main.cpp:328-334). */
 int rt_set_camera(struct rt_ctx* ctx, const FlatCamera* camera);
 int rt_set_light(struct rt_ctx* ctx, const FlatLight* light);
+
+/* More than one point light (an extension: the reference shader has one).
+ *
+ * rt_set_lights copies `count` records (1..RT_MAX_LIGHTS) and applies them at the next
+ * dispatch, as rt_set_light does; it replaces the whole set. rt_set_light(l) is
+ * rt_set_lights(l, 1), so a host that sets its light every frame (rth_render_loop*) keeps
+ * rendering one light. rt_get_lights copies min(cap, count) records to `lights` and the set's
+ * size to `*count`; either pointer may be NULL (cap is not read when `lights` is NULL); a
+ * context that never had a light reports 0. RT_ERR_INVALID for a NULL context, for NULL
+ * `lights` or a count outside 1..RT_MAX_LIGHTS in rt_set_lights, and for a negative cap; the
+ * previous set stays in force.
+ *
+ * Definition. A pixel is the reference shader's main() except the light term `pc` of a bounce
+ * that hit something. Every operation is float32 and none is contracted. With the hit point
+ * hp, the normal hn, the material m, the incoming direction ray.d and the shadow offset off of
+ * the branch (1e-3 with useBVH, 1e-5 for the brute-force branch), for light i = 0 .. L-1, in
+ * order:
+ *   - the shadow ray has origin hp + hn * off (the same for every light) and direction
+ *     normalize(pos_i - hp); it is blocked by an INNER hit nearer than
+ *     min(dist(pos_i, hp), 1e20f): the reference's shadow ray, with light i;
+ *   - term_i = phong(hp, hn, ray.d, pos_i, color_i, m), times 0.3f if blocked: the
+ *     reference's pc, with light i.
+ * Then pc = term_0, and pc = pc + term_i per component for i = 1 .. L-1, left to right. The
+ * rest of the bounce uses that pc exactly as the shader does: acc += att * pc, the mirror
+ * ray, Fresnel's second acc term, att. Phong's ambient term is per light (ambient * color_i /
+ * dist(pos_i, hp), gpu_shader.comp:331-361), so each light brings its own ambient. L = 1 is
+ * the reference's pixel, bit for bit, and runs exactly the kernels it ran before this call
+ * existed.
+ *
+ * The set applies to every frame dispatch (rt_dispatch, rt_dispatch_rows, _fmt, _ex) in every
+ * pixel and surface format, to frames under rt_set_samples and rt_set_adaptive, and to
+ * rt_shade_rays / rt_shade_rays_host. It does not enter rt_trace_*, rt_dispatch_gbuffer,
+ * rt_dispatch_ao or rt_camera_rays. rt_collect_stats* keeps counting the reference's
+ * one-light frame, with light 0. An rt_group's frames keep their one light
+ * (rt_group_set_light sets one).
+ *
+ * Frames and ray lists of two or more lights run in kernels of their own: over the
+ * accelerator (rt_accel_info::last_kernel reports RT_KERNEL_LIGHTS for a frame) camera rays
+ * and their L shadow rays walk as wave64 packets, later bounces per lane; RT_KERNEL_LANE /
+ * RT_KERNEL_PACKET, contexts without a usable accelerator and far cameras take the literal
+ * per-pixel loop (last_kernel reports RT_KERNEL_LANE). Both write the same bytes. For
+ * rt_set_samples such a frame is one the accelerated kernel does not render: the sample
+ * frame goes to the context's scratch surface and a filter pass writes the output (the
+ * adaptive filter under rt_set_adaptive). The cost order (rt_set_schedule), latency mode,
+ * tail compaction (rt_set_tail) and rt_set_walk do not apply to these frames.
+ * rt_kernel_times gets one entry per dispatch and rt_sync_frame's marker follows the frame,
+ * as for any frame. */
+enum { RT_MAX_LIGHTS = 8 };
+int rt_set_lights(struct rt_ctx* ctx, const FlatLight* lights, int count);
+int rt_get_lights(struct rt_ctx* ctx, FlatLight* lights, int cap, int* count);
 
 /* The five uniforms (src/main.cpp:357-361). */
 int rt_set_params(struct rt_ctx* ctx, const rt_params* params);

@@ -41,6 +41,24 @@ inline unsigned long long dispatch_pixels(const Frame& k) {
     return rows * static_cast<unsigned long long>(k.width);
 }
 
+// rt_set_lights: which kernels render a frame or a ray list of `lights` lights.
+enum LightsRoute {
+    kLightsOff,    // one light (or a stats dispatch): the existing kernels, nothing new on the device
+    kLightsAccel,  // k_lights over the accelerator (RT_KERNEL_LIGHTS)
+    kLightsRef     // k_lights_ref, the literal per-lane loop (RT_KERNEL_LANE)
+};
+
+// `accel`: the dispatch would otherwise go to the accelerated kernel (k_accel for a frame --
+// RT_KERNEL_AUTO / RT_KERNEL_ACCEL with a usable accelerator, camera within its bound --
+// k_shade for a list). rt_collect_stats* counts the reference's one-light frame whatever the set.
+inline LightsRoute lights_route(int lights, bool stats, bool accel) {
+    if (lights < 2 || stats) return kLightsOff;
+    return accel ? kLightsAccel : kLightsRef;
+}
+
+// A frame of two or more lights is, for samples_plan, one k_accel does not render: its `accel`.
+inline bool accel_renders(bool accel_kind, LightsRoute r) { return accel_kind && r == kLightsOff; }
+
 struct Samples {
     bool ss, ss_accel, adaptive, ad_fast, ss_fused, filter;
 };

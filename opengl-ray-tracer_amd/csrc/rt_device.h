@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "light_set.h"
 #include "srgb_table.h"
 
 namespace rtd {

@@ -44,6 +44,10 @@
 //       rt_camera_rays): the caller's rays through k_accel_tail's bounce loop from bounce 0,
 //       every walk per lane (k_shade), or through k_lane's literal loop (k_shade_ref), one
 //       compact pixel per ray; k_camera_rays writes a frame's own camera rays as such a list.
+//   k_lights<MT, DISP, FRAME> / k_lights_ref<DISP, FRAME> : frames and shaded rays of two or
+//       more point lights (rt_set_lights): the bounce loop with L shadow walks per bounce
+//       (bounce_step_lights). FRAME: one 8x8 tile per wave, camera rays and their shadow rays
+//       as packets, later bounces per lane; else k_shade's list. k_lights_ref is the literal loop.
 //   k_gbuffer<MT, LANE> / k_gbuffer_ref : geometry buffers (rt_dispatch_gbuffer): the closest
 //       hit of every pixel's camera ray as planes of shape, depth, normal and position. One
 //       8x8 tile per wave through packet_walk (or lane_walk for a camera beyond the
@@ -2247,6 +2251,226 @@ __global__ __launch_bounds__(kBlock) void k_camera_rays(KParams kp, float4* __re
 }
 
 // ---------------------------------------------------------------------------
+// Two or more point lights (rt_set_lights; the definition is include/rt_api.h's). Kernels of
+// their own: one-light frames and lists never reach this code, and nothing above is changed.
+
+__device__ __forceinline__ V light_pos(const LightSet& L, int i) { return mk(L.pos[i][0], L.pos[i][1], L.pos[i][2]); }
+__device__ __forceinline__ V light_col(const LightSet& L, int i) { return mk(L.col[i][0], L.col[i][1], L.col[i][2]); }
+
+// The light term of a bounce: term_0 + term_1 + ..., left to right, term_i = phong with light
+// i, times 0.3 where bit i of `blocked` is set. i is wave-uniform: scalar loads of the records.
+__device__ __forceinline__ V lights_term(const LightSet& L, V hp, V hn, V view, const Mat& m, unsigned blocked) {
+    V pc = mk(0.f, 0.f, 0.f);
+#pragma unroll 1
+    for (int i = 0; i < L.count; ++i) {
+        V t = phong(hp, hn, view, light_pos(L, i), light_col(L, i), m);
+        if ((blocked >> i) & 1u) t = t * 0.3f;
+        pc = i == 0 ? t : pc + t;
+    }
+    return pc;
+}
+
+// shade_bounce (gpu_shader.comp:482-516) from a light term already summed.
+__device__ __forceinline__ bool shade_bounce_pc(const KParams& kp, Ray& ray, V hp, V hn, const Mat& m, V pc, V& acc,
+                                                V& att, float offset_reflect) {
+    acc = acc + mulv(att, pc);
+    if (m.specular > 0.0f) {
+        V rd = reflect(ray.d, hn);
+        ray.o = hp + hn * offset_reflect;
+        ray.d = rd;
+        if (kp.useFresnel) {
+            float fr = powf(1.0f - gmax(dot(-ray.d, hn), 0.0f), 5.0f);
+            fr = gmin(gmax(fr, 0.0f), 0.8f);
+            float rw = m.fresnel * fr;
+            float mw = 1.0f - rw;
+            att = mulv(att, mix(m.color, mk(1.f, 1.f, 1.f), rw));
+            acc = acc + mulv(mw * m.color, pc);
+        } else {
+            att = att * m.specular;
+        }
+        return true;
+    }
+    return false;
+}
+
+// bounce_step with the light loop: the closest walk, then L shadow walks from the one shadow
+// origin, each lane's answers collected in `blocked`; only after the last walk are the normal
+// and the material fetched, once, and the Phong loop run. So what is live through the walks
+// is what bounce_step keeps live through its single shadow walk, plus one register. The
+// shadow ray is formed again from the hit record before each walk for the same reason.
+template <bool MT, class BgY>
+__device__ __forceinline__ void bounce_step_lights(const AccelPtrs& A, const float4* __restrict__ mat,
+                                                   const KParams& kp, const LightSet& L, int depth, Ray& ray,
+                                                   bool& alive, V& acc, V& att, BgY bg_y, int* stk, unsigned short* stt,
+                                                   int cap, WalkCount& wc, int lane_from, int shadow_from) {
+    Best best{1e20f, 0x7fffffff, 0.f, -1};
+    bool unused = false;
+    if (depth >= lane_from)  // wave-uniform
+        lane_walk_any<false, false, false, MT, false>(A, ray, alive, 0.f, best, unused, stk, stt, blockDim.x, cap, wc);
+    else
+        packet_walk<false, false, false, MT>(A, ray, alive, 0.f, best, unused, wc);
+    if (alive && best.slot < 0) {
+        acc = acc + mulv(att, background(kp, bg_y()));
+        alive = false;
+    }
+    unsigned blocked = 0;
+#pragma unroll 1
+    for (int i = 0; i < L.count; ++i) {
+        Ray sr{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 1.f)};
+        float ld = 0.f;
+        if (alive) {
+            const V hp = hit_point(ray, best.t);
+            const V hn = shape_normal(load_prim(A.prims, best.slot), hp);
+            const V lp = light_pos(L, i);
+            sr = Ray{hp + hn * kp.shadow_off, normalize(lp - hp)};
+            ld = dist(lp, hp);
+        }
+        bool shadow = false;
+        Best dummy{0.f, 0, 0.f, -1};
+        if (depth >= shadow_from)
+            lane_walk_any<true, false, false, MT, false>(A, sr, alive, gmin(ld, 1e20f), dummy, shadow, stk, stt,
+                                                         blockDim.x, cap, wc);
+        else
+            packet_walk<true, false, false, MT>(A, sr, alive, gmin(ld, 1e20f), dummy, shadow, wc);
+        if (shadow) blocked |= 1u << i;
+    }
+    if (alive) {
+        const PrimRec g = load_prim(A.prims, best.slot);
+        const V hp = hit_point(ray, best.t);
+        const V hn = shape_normal(g, hp);
+        const Mat m = load_mat(mat, A.prim_shape[best.slot]);
+        alive = shade_bounce_pc(kp, ray, hp, hn, m, lights_term(L, hp, hn, ray.d, m, blocked), acc, att, 1e-3f);
+    }
+}
+
+// Over the accelerator, one wave per block with the lane stacks in LDS, as k_shade.
+// FRAME = false: k_shade's shape -- ray i of the list per lane, every walk per lane, compact
+// pixels. FRAME = true: tile blockIdx.x of the frame in row-major tile order (tile_pixel,
+// primary_ray), camera rays and their L shadow rays as wave64 packets -- the L shadow packets
+// of a tile converge on one point each -- and later bounces per lane; the sky from the image
+// row, the pixel through store_px in the dispatch's row mapping and format. No cost order, no
+// split tiles, no compaction: launch_lights.
+template <bool MT, bool DISP, bool FRAME>
+__global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_lights(AccelPtrs A, const float4* __restrict__ mat,
+                                                                  ShadeArgs q, LightSet L, KParams kp) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    unsigned short* stt =
+        reinterpret_cast<unsigned short*>(lds_stack + static_cast<size_t>(kp.lane_stack) * blockDim.x) + threadIdx.x;
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;  // the list's ray
+    const int tile = static_cast<int>(blockIdx.x);             // the frame's tile
+    bool alive;
+    Ray ray{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 1.f)};
+    if constexpr (FRAME) {
+        const PixelCoord pc = tile_pixel(kp, tile);
+        ray = primary_ray(kp, pc.x, pc.y);
+        alive = pc.active;
+    } else {
+        alive = i < static_cast<unsigned>(q.n);
+        if (alive) {
+            const float4 a = q.rays[2 * static_cast<size_t>(i)], b = q.rays[2 * static_cast<size_t>(i) + 1];
+            ray = Ray{mk(a.x, a.y, a.z), mk(b.x, b.y, b.z)};
+        }
+    }
+    const bool have = alive;
+    V acc = mk(0.f, 0.f, 0.f), att = mk(1.f, 1.f, 1.f);
+    if (FRAME && kp.root_ok) {
+        // accel_tile's root test: a camera ray that misses the root's box takes the background
+        V rlo = mk(kp.root_lo[0], kp.root_lo[1], kp.root_lo[2]), rhi = mk(kp.root_hi[0], kp.root_hi[1], kp.root_hi[2]);
+        if (kp.root_ok == 2) {
+            const float4 a = A.anodes[4 * static_cast<size_t>(A.N - 1)], b = A.anodes[4 * static_cast<size_t>(A.N - 1) + 1];
+            rlo = mk(a.x, a.y, a.z);
+            rhi = mk(b.x, b.y, b.z);
+        }
+        if (alive && !ray_aabb(ray.o, inv_dir(ray.d), rlo, rhi)) {
+            acc = background(kp, tile_pixel(kp, tile).y);
+            alive = false;
+        }
+    }
+    WalkCount wc{0u, 0u, 0u, 0u};
+    for (int depth = 0; depth < kp.maxBounces; ++depth) {
+        if (__ballot(alive) == 0) break;
+        if constexpr (FRAME)
+            bounce_step_lights<MT>(A, mat, kp, L, depth, ray, alive, acc, att,
+                                   [&]() { return tile_pixel(kp, tile).y; }, stk, stt, kp.lane_stack, wc, 1, 1);
+        else
+            bounce_step_lights<MT>(A, mat, kp, L, depth, ray, alive, acc, att,
+                                   [&]() { return q.rays[2 * static_cast<size_t>(i)].w; }, stk, stt, kp.lane_stack,
+                                   wc, 0, 0);
+    }
+    if (!have) return;
+    const float4 px = make_float4(acc.x, acc.y, acc.z, 1.0f);
+    if constexpr (FRAME) {
+        const PixelCoord pc = tile_pixel(kp, tile);
+        store_px<DISP ? kStoreDisplay : kStoreFloat>(kp, pc.r, pc.x, px);
+    } else {
+        store_px<DISP ? kStoreDisplay : kStoreFloat>(kp, shade_row(i), shade_col(i), px);
+    }
+}
+
+// The literal per-lane loop of k_lane (FRAME: its pixels and blocks) / k_shade_ref (the list)
+// with the light loop, both useBVH branches: RT_KERNEL_LANE / RT_KERNEL_PACKET, contexts
+// without a usable accelerator, far cameras. The BVH branch's shadow is the full closest-hit
+// walk with found && d < ld, per light (gpu_shader.comp:473-480).
+template <bool DISP, bool FRAME>
+__global__ __launch_bounds__(kBlock) void k_lights_ref(ShadeArgs q, LightSet L, KParams kp) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    int r, x;  // the output pixel
+    V bg;
+    Ray ray;
+    if constexpr (FRAME) {
+        const PixelCoord pc = pixel_of(kp);
+        if (!pc.active) return;
+        r = pc.r;
+        x = pc.x;
+        bg = background(kp, pc.y);
+        ray = primary_ray(kp, pc.x, pc.y);
+    } else {
+        if (i >= static_cast<unsigned>(q.n)) return;
+        const float4 ra = q.rays[2 * static_cast<size_t>(i)], rb = q.rays[2 * static_cast<size_t>(i) + 1];
+        r = shade_row(i);
+        x = shade_col(i);
+        bg = background(kp, ra.w);
+        ray = Ray{mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z)};
+    }
+    V acc = mk(0.f, 0.f, 0.f), att = mk(1.f, 1.f, 1.f);
+    Counters c;
+    const float shadow_off = kp.useBVH ? 1e-3f : 1e-5f;  // :469 vs :565
+    for (int depth = 0; depth < kp.maxBounces; ++depth) {
+        const LaneHit hit = kp.useBVH ? lane_closest_bvh<false>(kp, kp.nodes, kp.geo_leaf, ray, stk, c)
+                                      : lane_closest_brute<false>(kp, kp.geo_lin, ray, c);
+        if (!hit.found) {
+            acc = acc + mulv(att, bg);
+            break;
+        }
+        const GeoRec g = load_rec(kp.useBVH ? kp.geo_leaf : kp.geo_lin, hit.slot);
+        const V hn = shape_normal(g, hit.p);
+        const Mat m = load_mat(kp.mat, g.idx);
+        const V so = hit.p + hn * shadow_off;
+        unsigned blocked = 0;
+#pragma unroll 1
+        for (int k = 0; k < L.count; ++k) {
+            const V lp = light_pos(L, k);
+            const Ray sr{so, normalize(lp - hit.p)};
+            const float ld = dist(lp, hit.p);
+            bool shadow;
+            if (kp.useBVH) {
+                const LaneHit sh = lane_closest_bvh<false>(kp, kp.nodes, kp.geo_leaf, sr, stk, c);
+                shadow = sh.found && sh.d < ld;
+            } else {
+                shadow = lane_shadow_brute<false>(kp, kp.geo_lin, sr, ld, c);
+            }
+            if (shadow) blocked |= 1u << k;
+        }
+        if (!shade_bounce_pc(kp, ray, hit.p, hn, m, lights_term(L, hit.p, hn, ray.d, m, blocked), acc, att, 1e-3f))
+            break;
+    }
+    store_px<DISP ? kStoreDisplay : kStoreFloat>(kp, r, x, make_float4(acc.x, acc.y, acc.z, 1.0f));
+}
+
+// ---------------------------------------------------------------------------
 // Geometry buffers (rt_dispatch_gbuffer / rt_gbuffer_host): the closest hit of every pixel's
 // camera ray as up to four planes (include/rt_api.h: shape, depth, normal, position).
 
@@ -3584,7 +3808,9 @@ struct rt_ctx {
     rta::AccelHost accel;
     // frame constants
     FlatCamera cam{};
-    FlatLight light{};
+    FlatLight light{};                       // light 0: the one light of every existing kernel
+    FlatLight lights[RT_MAX_LIGHTS]{};       // rt_set_lights: the whole set (lights[0] == light)
+    int nlights = 1;                         // its size; >= 2: the k_lights kernels (rtp::lights_route)
     rt_params params{0.f, 0.f, 0, 0, 0, 0};  // the reference's first frame sees zeros
     bool have_params = false;                // rt_set_params was called (rt_trace_pixels needs resX / resY)
     // rt_trace_rays_host / rt_trace_pixels: staging for the rays (or pixels) and the hits,
@@ -4703,6 +4929,8 @@ rt_ctx* sub_ctx(rt_ctx* c, rt_ctx*& sub, bool& stale) {
 void inherit(rt_ctx* b, const rt_ctx* c) {
     b->cam = c->cam;
     b->light = c->light;
+    std::copy(c->lights, c->lights + RT_MAX_LIGHTS, b->lights);
+    b->nlights = c->nlights;
     b->have_cam = b->have_light = true;
     b->params = c->params;
     b->kernel = RT_KERNEL_ACCEL;
@@ -5168,6 +5396,30 @@ int launch_accel(rt_ctx* c, const KParams& kin, const KParams& kout, const KPara
     return k2.tile_cost ? launch_cost_order(c, k2, latency, dilate, span) : RT_OK;
 }
 
+// launch()'s render of a frame of two or more lights (rtp::lights_route): k_lights over the
+// context's accelerator, one wave per 8x8 tile in row-major order, or k_lights_ref on k_lane's
+// grid. The set is the context's (a sub-context inherits its parent's). No cost order, no
+// latency mode, no compaction, no walk policy: the frame's walks are fixed (k_lights).
+void launch_lights(rt_ctx* c, const KParams& kp, bool accel, dim3 lane_grid) {
+    const LightSet L = make_light_set(c->lights, c->nlights);
+    const ShadeArgs q{nullptr, 0};
+    const bool disp = kp.rgb >= RT_FORMAT_RGBA8;
+    if (!accel) {
+        auto kfn = disp ? k_lights_ref<true, true> : k_lights_ref<false, true>;
+        hipLaunchKernelGGL(kfn, lane_grid, dim3(kBlock), ref_stack_lds(kp), c->stream, q, L, kp);
+        return;
+    }
+    KParams k2 = kp;
+    k2.tiles_x = (kp.width + 7) / 8;
+    k2.tiles = k2.tiles_x * ((kp.out_rows + 7) / 8);
+    k2.root_ok = 0;  // (not with maxBounces = 0: launch_accel)
+    if (kp.maxBounces > 0 && kp.useBVH) root_bounds(c, k2);
+    k2.lane_stack = lane_stack_entries(c);
+    auto kfn = c->accel.mt ? (disp ? k_lights<true, true, true> : k_lights<true, false, true>)
+                           : (disp ? k_lights<false, true, true> : k_lights<false, false, true>);
+    hipLaunchKernelGGL(kfn, dim3(k2.tiles), dim3(64), lane_stack_lds(k2), c->stream, accel_ptrs(c), c->mat, q, L, k2);
+}
+
 int launch(rt_ctx* c, const KParams& kin, bool stats) {
     c->frame_ev_set = false;
     c->ad_ran = false;
@@ -5179,9 +5431,12 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
     const bool usable = accel_usable(c, kin);
     if (kind == RT_KERNEL_AUTO) kind = usable ? RT_KERNEL_ACCEL : RT_KERNEL_PACKET;
     if (kind == RT_KERNEL_ACCEL && !usable) kind = RT_KERNEL_PACKET;  // same image either way
+    // rt_set_lights: two or more lights render in k_lights / k_lights_ref; one light takes
+    // every path below as it always did
+    const rtp::LightsRoute lr = rtp::lights_route(c->nlights, stats, kind == RT_KERNEL_ACCEL);
     const rtp::Samples sp =
-        rtp::samples_plan(stats, kin.ss, kind == RT_KERNEL_ACCEL, c->tile_times != nullptr, c->ss_general,
-                          c->adaptive >= 0.0f, c->convert_pass, kin.rgb >= RT_FORMAT_RGBA8);
+        rtp::samples_plan(stats, kin.ss, rtp::accel_renders(kind == RT_KERNEL_ACCEL, lr), c->tile_times != nullptr,
+                          c->ss_general, c->adaptive >= 0.0f, c->convert_pass, kin.rgb >= RT_FORMAT_RGBA8);
     KParams kout = kin;  // adaptive: the one-sample output frame, B's, with the dispatch's dst / pitch / format
     if (sp.adaptive) {
         set_frame(kout, rtp::output_frame(frame_of(kin), kin.ss));
@@ -5223,6 +5478,10 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
     if (stats) {
         hipLaunchKernelGGL(k_lane<true>, grid, dim3(kBlock), lds, c->stream, c->geo_leaf, c->geo_lin, c->mat,
                            c->nodes, kp);
+    } else if (lr != rtp::kLightsOff) {
+        launch_lights(c, kp, lr == rtp::kLightsAccel, grid);
+        if (sp.filter) launch_box_filter(c, kin);
+        kind = lr == rtp::kLightsAccel ? RT_KERNEL_LIGHTS : RT_KERNEL_LANE;
     } else if (kind == RT_KERNEL_LANE) {
         hipLaunchKernelGGL(k_lane<false>, grid, dim3(kBlock), lds, c->stream, c->geo_leaf, c->geo_lin, c->mat,
                            c->nodes, kp);
@@ -5546,7 +5805,19 @@ int shade_launch(rt_ctx* c, const float4* rays, int n, void* pixels, int format)
     kp.heavy_parts = 1;
     const ShadeArgs q{rays, n};
     const bool disp = format >= RT_FORMAT_RGBA8;
-    if (accel) {
+    // rt_set_lights: two or more lights (this context's set) in k_lights' list form, over the
+    // same target; one light takes k_shade / k_shade_ref as it always did
+    const rtp::LightsRoute lr = rtp::lights_route(c->nlights, false, accel);
+    if (lr == rtp::kLightsAccel) {
+        auto kfn = mt ? (disp ? k_lights<true, true, false> : k_lights<true, false, false>)
+                      : (disp ? k_lights<false, true, false> : k_lights<false, false, false>);
+        hipLaunchKernelGGL(kfn, dim3((static_cast<unsigned>(n) + 63u) / 64u), dim3(64), lane_stack_lds(kp), c->stream,
+                           accel_ptrs(t), t->mat, q, make_light_set(c->lights, c->nlights), kp);
+    } else if (lr == rtp::kLightsRef) {
+        auto kfn = disp ? k_lights_ref<true, false> : k_lights_ref<false, false>;
+        hipLaunchKernelGGL(kfn, dim3((static_cast<unsigned>(n) + kBlock - 1u) / kBlock), dim3(kBlock), ref_stack_lds(kp),
+                           c->stream, q, make_light_set(c->lights, c->nlights), kp);
+    } else if (accel) {
         const bool split = !mt && (c->shade_split ? c->shade_split == 2 : t->accel.st.item_ref.size() >= kShadeSplitItems);
         auto kfn = mt      ? (disp ? k_shade<true, false, true> : k_shade<true, false, false>)
                    : split ? (disp ? k_shade<false, true, true> : k_shade<false, true, false>)
@@ -6077,10 +6348,23 @@ int rt_set_camera(rt_ctx* c, const FlatCamera* cam) {
     return RT_OK;
 }
 
-int rt_set_light(rt_ctx* c, const FlatLight* l) {
-    if (!c || !l) return RT_ERR_INVALID;
-    c->light = *l;
+int rt_set_light(rt_ctx* c, const FlatLight* l) { return rt_set_lights(c, l, 1); }
+
+int rt_set_lights(rt_ctx* c, const FlatLight* lights, int count) {
+    if (!c || !lights || count < 1 || count > RT_MAX_LIGHTS) return RT_ERR_INVALID;
+    for (int i = 0; i < RT_MAX_LIGHTS; ++i) c->lights[i] = i < count ? lights[i] : FlatLight{};
+    c->light = c->lights[0];
+    c->nlights = count;
     c->have_light = true;
+    return RT_OK;
+}
+
+int rt_get_lights(rt_ctx* c, FlatLight* lights, int cap, int* count) {
+    if (!c || (lights && cap < 0)) return RT_ERR_INVALID;
+    const int n = c->have_light ? c->nlights : 0;
+    if (lights)
+        for (int i = 0; i < std::min(cap, n); ++i) lights[i] = c->lights[i];
+    if (count) *count = n;
     return RT_OK;
 }
 

@@ -96,6 +96,8 @@ VIEW_RAY_DTYPE = np.dtype({
 SPHERE, PLANE, WALL, TRIANGLE = 0, 1, 2, 3
 TRACE_CLOSEST, TRACE_ANY = 0, 1
 KERNEL_AUTO, KERNEL_LANE, KERNEL_PACKET, KERNEL_ACCEL = 0, 1, 2, 3
+KERNEL_LIGHTS = 4  # reported by accel_info()["last_kernel"] only: a frame of two or more lights (set_lights)
+MAX_LIGHTS = 8     # RT_MAX_LIGHTS
 SCHED_ROWS, SCHED_COST, SCHED_COST_XCD = 0, 1, 2
 TREE_REFERENCE, TREE_SCENE = 0, 1
 
@@ -249,6 +251,7 @@ RT_SYMBOLS = {
     "rt_set_animated": (_I, [_P, _P, _I]), "rt_animate": (_I, [_P, _P]),
     "rt_read_nodes": (_I, [_P, _P, _I]),
     "rt_set_camera": (_I, [_P, _P]), "rt_set_light": (_I, [_P, _P]),
+    "rt_set_lights": (_I, [_P, _P, _I]), "rt_get_lights": (_I, [_P, _P, _I, _P]),
     "rt_set_params": (_I, [_P, _P]), "rt_set_kernel": (_I, [_P, _I]),
     "rt_dispatch": (_I, [_P, _I, _I, _I, _I]),
     "rt_dispatch_rows": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t]),
@@ -707,6 +710,19 @@ class ComputeShader:
     def set_light(self, light):
         light = as_records(light, LIGHT_DTYPE)
         self._chk(self._lib.rt_set_light(self._h, _ptr(light)), "rt_set_light")
+
+    def set_lights(self, lights):
+        """rt_set_lights: 1..MAX_LIGHTS point lights (LIGHT_DTYPE records) from the next dispatch
+        on, replacing the whole set; one record is set_light."""
+        lights = as_records(lights, LIGHT_DTYPE).reshape(-1)
+        self._chk(self._lib.rt_set_lights(self._h, _ptr(lights), len(lights)), "rt_set_lights")
+
+    def get_lights(self):
+        """rt_get_lights: the set in force as LIGHT_DTYPE records."""
+        out = np.zeros(MAX_LIGHTS, LIGHT_DTYPE)
+        n = C.c_int()
+        self._chk(self._lib.rt_get_lights(self._h, _ptr(out), MAX_LIGHTS, C.byref(n)), "rt_get_lights")
+        return out[:n.value]
 
     def set_params(self, resX, resY, maxBounces=3, useBVH=True, useFresnel=False, useMollerTrumbore=False):
         p = rt_params(float(resX), float(resY), int(maxBounces), int(bool(useBVH)), int(bool(useFresnel)),
