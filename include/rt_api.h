@@ -55,9 +55,12 @@ enum rt_kernel {
     RT_KERNEL_PACKET = 2,    /* wave64 packet walk, wave-uniform stack + active mask  */
     RT_KERNEL_ACCEL = 3,     /* packet walk + exact-result leaf accelerator (default  */
                              /* for BVH + barycentric; falls back to PACKET otherwise)*/
-    RT_KERNEL_LIGHTS = 4     /* reported only (rt_accel_info::last_kernel): the frame */
+    RT_KERNEL_LIGHTS = 4,    /* reported only (rt_accel_info::last_kernel): the frame */
                              /* of two or more lights over the accelerator            */
                              /* (rt_set_lights); rt_set_kernel does not take it       */
+    RT_KERNEL_SOFT = 5       /* reported only: the frame of area lights over the      */
+                             /* accelerator (rt_set_soft_shadows); rt_set_kernel does */
+                             /* not take it                                           */
 };
 
 /* Accelerator statistics of the uploaded scene (rt_accel_info). */
@@ -208,6 +211,79 @@ int rt_set_light(struct rt_ctx* ctx, const FlatLight* light);
 enum { RT_MAX_LIGHTS = 8 };
 int rt_set_lights(struct rt_ctx* ctx, const FlatLight* lights, int count);
 int rt_get_lights(struct rt_ctx* ctx, FlatLight* lights, int cap, int* count);
+
+/* Area lights: soft shadows from K shadow rays per light (an extension: the reference shader's
+ * lights are points and its shadows hard edges).
+ *
+ * rt_set_soft_shadows gives light i of the set in force (rt_set_lights / rt_set_light) the
+ * radius radii[i], i < count; lights with index >= count have radius 0. count is
+ * 0..RT_MAX_LIGHTS, every radius finite and >= 0, `samples` is K, 1..RT_MAX_SHADOW_SAMPLES.
+ * count == 0 (radii may be NULL, samples is not read) turns the feature off; off is the default.
+ * The setting belongs to the context, like rt_set_samples: it is applied at the next dispatch
+ * and survives rt_set_lights, rt_set_light and rt_upload_scene. rt_get_soft_shadows mirrors
+ * rt_get_lights: min(cap, count) radii to `radii`, the count to `*count`, K to `*samples` (0
+ * while the feature is off); any pointer may be NULL, cap is not read when `radii` is NULL.
+ * RT_ERR_INVALID for a NULL context, NULL radii with count > 0, a count outside
+ * 0..RT_MAX_LIGHTS, samples outside 1..RT_MAX_SHADOW_SAMPLES when count > 0, a negative, NaN or
+ * infinite radius, and a negative cap; the previous setting stays in force.
+ *
+ * When it is active. A dispatch or ray list is soft iff some light i < L (L the light set's
+ * size) has radius[i] > 0. One that is not soft runs exactly the kernels it runs without this
+ * call, byte for byte; a soft one runs kernels of its own, for L = 1 as well.
+ *
+ * Definition. A soft pixel is rt_set_lights' pixel except for the shadow factor of each light.
+ * Every operation is float32, in the order written, and none is contracted. At a bounce, with
+ * the hit point hp, the normal hn and the shadow origin so = hp + hn * off (unchanged: 1e-3
+ * with useBVH, 1e-5 on the brute-force branch), for light i with position pos_i, radius R_i:
+ *   - R_i == 0: one shadow ray, exactly rt_set_lights' ray. K_i = 1, and b_i is 1 if the ray
+ *     is blocked, else 0.
+ *   - R_i > 0: K_i = K, and b_i is the number of blocked sample rays k = 0..K-1. Sample ray k:
+ *     1. w = normalize(pos_i - hp), the hard shadow ray's direction, the same expression.
+ *     2. The tangent frame (t, u) about w is step 2 of rt_dispatch_ao's definition with
+ *        nf := w (no facing flip):
+ *          sg = copysignf(1, w.z)
+ *          a  = -1.0f / (sg + w.z)
+ *          b  = (w.x*w.y)*a
+ *          t  = (1.0f + sg*((w.x*w.x)*a), sg*b, -(sg*w.x))
+ *          u  = (b, sg + (w.y*w.y)*a, -w.y)
+ *     3. The rotation is (c, sn) = ROT[j] of rt_dispatch_ao's table, with
+ *          j = (((bits(hp.x) ^ bits(hp.y) ^ bits(hp.z)) * 0x9E3779B1u) mod 2^32) >> 28.
+ *        j comes from the hit point, not from the pixel: a ray list and a frame agree, and so
+ *        do reflected hits.
+ *     4. The disc point comes from D[k].x, D[k].y of rt_dispatch_ao's table (the x, y of
+ *        cosine-weighted hemisphere points are uniform on the unit disc):
+ *          lx = c*D[k].x - sn*D[k].y
+ *          ly = sn*D[k].x + c*D[k].y
+ *          rx = R_i*lx
+ *          ry = R_i*ly
+ *     5. The sample point, per component: s.c = pos_i.c + ((t.c*rx) + (u.c*ry)). It lies on a
+ *        disc of radius R_i about the light that faces the hit.
+ *     6. The ray has origin so and direction normalize(s - hp). It is blocked by an INNER hit
+ *        nearer than min(dist(s, hp), 1e20f): the hard ray's test with s in place of pos_i.
+ *   - term_i = phong(hp, hn, ray.d, pos_i, color_i, m): Phong uses the centre, once per light.
+ *     If b_i > 0, term_i is multiplied by 1.0f - 0.7f * ((float)b_i / (float)K_i). For
+ *     b_i == K_i that factor is 1.0f - 0.7f, in float32 exactly 0.3f: a fully blocked light
+ *     has the hard shadow's bits.
+ * Then pc = term_0, and pc = pc + term_i left to right; the rest of the bounce is the shader's.
+ *
+ * Limits. The penumbra is K discrete levels, dithered by a hash of the hit point: noise, not a
+ * pattern, and rt_set_samples averages it. The disc is not clipped against the surface's
+ * horizon.
+ *
+ * It applies to every frame dispatch form in every pixel and surface format, to frames under
+ * rt_set_samples and rt_set_adaptive (such a frame is one the accelerated kernel does not
+ * render, as with lights: a scratch sample frame, then the filter or adaptive filter pass) and
+ * to rt_shade_rays / rt_shade_rays_host. It does not enter rt_trace_*, rt_dispatch_gbuffer,
+ * rt_dispatch_ao, rt_camera_rays, rt_collect_stats* or an rt_group's frames. The cost order,
+ * latency mode, rt_set_tail and rt_set_walk do not apply to soft frames. rt_kernel_times gets
+ * one entry per dispatch and rt_sync_frame's marker follows the frame;
+ * rt_accel_info::last_kernel reports RT_KERNEL_SOFT over the accelerator (camera rays and all
+ * their sample rays walk as wave64 packets, later bounces per lane) and RT_KERNEL_LANE for the
+ * literal loop (RT_KERNEL_LANE / RT_KERNEL_PACKET, contexts without a usable accelerator, far
+ * cameras). Both write the same bytes. */
+enum { RT_MAX_SHADOW_SAMPLES = 64 };
+int rt_set_soft_shadows(struct rt_ctx* ctx, const float* radii, int count, int samples);
+int rt_get_soft_shadows(struct rt_ctx* ctx, float* radii, int cap, int* count, int* samples);
 
 /* The five uniforms (src/main.cpp:357-361). */
 int rt_set_params(struct rt_ctx* ctx, const rt_params* params);

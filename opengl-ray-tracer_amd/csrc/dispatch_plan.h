@@ -59,6 +59,35 @@ inline LightsRoute lights_route(int lights, bool stats, bool accel) {
 // A frame of two or more lights is, for samples_plan, one k_accel does not render: its `accel`.
 inline bool accel_renders(bool accel_kind, LightsRoute r) { return accel_kind && r == kLightsOff; }
 
+// rt_set_soft_shadows: which kernels render a frame or a ray list of `lights` lights with the
+// radii `radii` (RT_MAX_LIGHTS of them; nullptr: none set). Consulted before lights_route.
+enum SoftRoute {
+    kSoftOff,    // no light of the set has a radius > 0 (or a stats dispatch): lights_route decides
+    kSoftAccel,  // k_soft over the accelerator (RT_KERNEL_SOFT)
+    kSoftRef     // k_soft_ref, the literal per-lane loop (RT_KERNEL_LANE)
+};
+
+// Soft iff some light i < lights has radii[i] > 0 -- one light included; a radius at an index
+// past the set does not count. `stats`, `accel`: as for lights_route.
+inline SoftRoute soft_route(int lights, const float* radii, bool stats, bool accel) {
+    bool soft = false;
+    for (int i = 0; radii && i < lights && i < RT_MAX_LIGHTS; ++i) soft = soft || radii[i] > 0.0f;
+    if (!soft || stats) return kSoftOff;
+    return accel ? kSoftAccel : kSoftRef;
+}
+
+// k_soft's form for the sample rays of bounces >= 1: repacked over the wave (true) or per live
+// lane. `form`: rt_debug_soft (1 = repacked, 2 = per lane, 0 = this rule). The repacked instance
+// wins where there are later bounces (car 1920x1080, 3 bounces: 6-15 % faster; 100k triangles:
+// 3-7 % at K >= 8) but its frame form spills, which costs 6-10 % on a frame of camera rays and
+// shadows only (the monkey scene, 1 bounce), where nothing is repacked: so by maxBounces.
+inline bool soft_repack(int form, int max_bounces) { return form == 0 ? max_bounces >= 2 : form == 1; }
+
+// A soft frame is, for samples_plan, one k_accel does not render either.
+inline bool accel_renders(bool accel_kind, LightsRoute r, SoftRoute s) {
+    return accel_renders(accel_kind, r) && s == kSoftOff;
+}
+
 struct Samples {
     bool ss, ss_accel, adaptive, ad_fast, ss_fused, filter;
 };

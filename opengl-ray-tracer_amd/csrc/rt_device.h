@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "light_set.h"
+#include "soft_set.h"
 #include "srgb_table.h"
 
 namespace rtd {

@@ -48,6 +48,9 @@
 //       more point lights (rt_set_lights): the bounce loop with L shadow walks per bounce
 //       (bounce_step_lights). FRAME: one 8x8 tile per wave, camera rays and their shadow rays
 //       as packets, later bounces per lane; else k_shade's list. k_lights_ref is the literal loop.
+//   k_soft<MT, DISP, FRAME> / k_soft_ref<DISP, FRAME> : frames and shaded rays of area lights
+//       (rt_set_soft_shadows): k_lights' shapes with K shadow walks per light of radius > 0
+//       (bounce_step_soft), the blocked rays counted per light.
 //   k_gbuffer<MT, LANE> / k_gbuffer_ref : geometry buffers (rt_dispatch_gbuffer): the closest
 //       hit of every pixel's camera ray as planes of shape, depth, normal and position. One
 //       8x8 tile per wave through packet_walk (or lane_walk for a camera beyond the
@@ -2743,6 +2746,292 @@ __global__ __launch_bounds__(kBlock) void k_ao_ref(AoArgs q, KParams kp) {
     store_ao(q, pc.r, pc.x, count);
 }
 
+// ---------------------------------------------------------------------------
+// Area lights (rt_set_soft_shadows; the definition is include/rt_api.h's, every operation below
+// in that order). Kernels of their own, in the shape of k_lights / k_lights_ref: frames and
+// lists without a radius > 0 never reach this code, and nothing above is changed.
+
+// Steps 1-5: sample point k of a light at lp with radius R > 0, seen from the hit point hp. The
+// frame is ao_frame's about w without the facing flip; the rotation is per lane (a hash of hp,
+// a gather from kAoRot), k is wave-uniform (scalar loads from kAoDir).
+__device__ __forceinline__ V soft_point(V hp, V lp, float R, int k) {
+    const V w = normalize(lp - hp);
+    const float sg = copysignf(1.0f, w.z);
+    const float a = -1.0f / (sg + w.z);
+    const float b = (w.x * w.y) * a;
+    const V t = mk(1.0f + sg * ((w.x * w.x) * a), sg * b, -(sg * w.x));
+    const V u = mk(b, sg + (w.y * w.y) * a, -w.y);
+    const unsigned j =
+        ((__float_as_uint(hp.x) ^ __float_as_uint(hp.y) ^ __float_as_uint(hp.z)) * 0x9E3779B1u) >> 28;
+    const float c = kAoRot[2 * j], sn = kAoRot[2 * j + 1];
+    const float dx = kAoDir[3 * k], dy = kAoDir[3 * k + 1];
+    const float lx = c * dx - sn * dy, ly = sn * dx + c * dy;
+    const float rx = R * lx, ry = R * ly;
+    return mk(lp.x + ((t.x * rx) + (u.x * ry)), lp.y + ((t.y * rx) + (u.y * ry)), lp.z + ((t.z * rx) + (u.z * ry)));
+}
+
+// Shadow ray k of light i from the hit (hp, hn): towards the sample point, or the light itself
+// for radius 0 -- then exactly k_lights' ray. `ld`: its limit before min(.., 1e20f).
+__device__ __forceinline__ Ray soft_ray(const LightSet& L, const SoftSet& S, int i, int k, V hp, V hn, float off,
+                                        float& ld) {
+    const V lp = light_pos(L, i);
+    const float R = S.radius[i];
+    const V s = R > 0.0f ? soft_point(hp, lp, R, k) : lp;
+    ld = dist(s, hp);
+    return Ray{hp + hn * off, normalize(s - hp)};
+}
+
+// The rays of light i: K for an area light, one for a point.
+__device__ __forceinline__ int soft_rays(const SoftSet& S, int i) { return S.radius[i] > 0.0f ? S.samples : 1; }
+
+// The light term of a bounce: term_0 + term_1 + ..., left to right; term_i = phong with light
+// i's centre, times 1 - 0.7 b_i / K_i where b_i > 0. `blocked`: eight 7-bit counts b_i.
+__device__ __forceinline__ V soft_term(const LightSet& L, const SoftSet& S, V hp, V hn, V view, const Mat& m,
+                                       unsigned long long blocked) {
+    V pc = mk(0.f, 0.f, 0.f);
+#pragma unroll 1
+    for (int i = 0; i < L.count; ++i) {
+        V t = phong(hp, hn, view, light_pos(L, i), light_col(L, i), m);
+        const unsigned b = static_cast<unsigned>(blocked >> (7 * i)) & 127u;
+        if (b > 0) t = t * (1.0f - 0.7f * (static_cast<float>(b) / static_cast<float>(soft_rays(S, i))));
+        pc = i == 0 ? t : pc + t;
+    }
+    return pc;
+}
+
+// bounce_step_lights with the sample loop: the closest walk, then K_i shadow walks per light
+// from the one shadow origin, each lane's blocked rays counted in `blocked` (two registers);
+// the normal and the material are fetched once, after the last walk, and each sample ray is
+// formed again from the hit record before its walk, so the walks keep live what
+// bounce_step_lights keeps. Both loops are wave-uniform. A wave whose lanes all left (sky)
+// walks no shadow ray.
+//   PACK (bounces >= 1, where a mirror leaves few lanes alive and each would walk its L K rays
+//   while the rest idle; k_ao's PACK form): the h live lanes leave hit point and normal in LDS
+//   (`pk`, slot = rank among the live lanes); per light the wave walks the h * K_i items 64 at
+//   a time (item: ray item / h of slot item % h), each sample ray formed from the slot by the
+//   same soft_ray, and adds each blocked ray to its owner's LDS counter, between wave-level
+//   fences. Same counts, so the same bytes.
+constexpr int kSoftSlot = 7;  // dwords a live lane leaves in LDS (PACK): hp, hn, its counter
+template <bool MT, bool PACK, class BgY>
+__device__ __forceinline__ void bounce_step_soft(const AccelPtrs& A, const float4* __restrict__ mat, const KParams& kp,
+                                                 const LightSet& L, const SoftSet& S, int depth, Ray& ray, bool& alive,
+                                                 V& acc, V& att, BgY bg_y, int* stk, unsigned short* stt, int cap,
+                                                 WalkCount& wc, int lane_from, int shadow_from, float* pk) {
+    Best best{1e20f, 0x7fffffff, 0.f, -1};
+    bool unused = false;
+    if (depth >= lane_from)  // wave-uniform
+        lane_walk_any<false, false, false, MT, false>(A, ray, alive, 0.f, best, unused, stk, stt, blockDim.x, cap, wc);
+    else
+        packet_walk<false, false, false, MT>(A, ray, alive, 0.f, best, unused, wc);
+    if (alive && best.slot < 0) {
+        acc = acc + mulv(att, background(kp, bg_y()));
+        alive = false;
+    }
+    const unsigned long long hm = __ballot(alive);
+    if (hm == 0) return;
+    unsigned long long blocked = 0;
+    if (PACK && depth >= 1) {  // wave-uniform: the live lanes' sample rays over all 64 lanes
+        const int lane = threadIdx.x & 63;
+        int* cnt = reinterpret_cast<int*>(pk) + 6 * 64;
+        const int h = __popcll(hm);
+        const int slot = __popcll(hm & ((1ull << lane) - 1ull));
+        if (alive) {
+            const V hp = hit_point(ray, best.t);
+            const V hn = shape_normal(load_prim(A.prims, best.slot), hp);
+            const float v[6] = {hp.x, hp.y, hp.z, hn.x, hn.y, hn.z};
+#pragma unroll
+            for (int e = 0; e < 6; ++e) pk[e * 64 + slot] = v[e];
+            cnt[slot] = 0;
+        }
+#pragma unroll 1
+        for (int i = 0; i < L.count; ++i) {
+            // the wave's own LDS writes, read by its other lanes: program order, no block barrier
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const unsigned items = static_cast<unsigned>(h) * static_cast<unsigned>(soft_rays(S, i));  // at most 4096
+#pragma unroll 1
+            for (unsigned base = 0; base < items; base += 64) {
+                const unsigned it = base + static_cast<unsigned>(lane);
+                const bool on = it < items;
+                const unsigned k = on ? it / static_cast<unsigned>(h) : 0u;
+                const int j = on ? static_cast<int>(it - k * static_cast<unsigned>(h)) : 0;
+                const V hp = mk(pk[0 * 64 + j], pk[1 * 64 + j], pk[2 * 64 + j]);
+                const V hn = mk(pk[3 * 64 + j], pk[4 * 64 + j], pk[5 * 64 + j]);
+                float ld;
+                Ray sr = soft_ray(L, S, i, static_cast<int>(k), hp, hn, kp.shadow_off, ld);
+                bool shadow = false;
+                Best dummy{0.f, 0, 0.f, -1};
+                lane_walk_any<true, false, false, MT, false>(A, sr, on, gmin(ld, 1e20f), dummy, shadow, stk, stt,
+                                                             blockDim.x, cap, wc);
+                if (on && shadow) atomicAdd(&cnt[j], 1);  // LDS atomic
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (alive) {
+                blocked += static_cast<unsigned long long>(cnt[slot]) << (7 * i);
+                cnt[slot] = 0;
+            }
+        }
+    }
+    const bool packed = PACK && depth >= 1;  // else the plain form: each live lane walks its own rays
+#pragma unroll 1
+    for (int i = 0; !packed && i < L.count; ++i) {
+        const int rays = soft_rays(S, i);
+#pragma unroll 1
+        for (int k = 0; k < rays; ++k) {
+            Ray sr{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 1.f)};
+            float ld = 0.f;
+            if (alive) {
+                const V hp = hit_point(ray, best.t);
+                sr = soft_ray(L, S, i, k, hp, shape_normal(load_prim(A.prims, best.slot), hp), kp.shadow_off, ld);
+            }
+            bool shadow = false;
+            Best dummy{0.f, 0, 0.f, -1};
+            if (depth >= shadow_from)
+                lane_walk_any<true, false, false, MT, false>(A, sr, alive, gmin(ld, 1e20f), dummy, shadow, stk, stt,
+                                                             blockDim.x, cap, wc);
+            else
+                packet_walk<true, false, false, MT>(A, sr, alive, gmin(ld, 1e20f), dummy, shadow, wc);
+            if (shadow) blocked += 1ull << (7 * i);
+        }
+    }
+    if (alive) {
+        const PrimRec g = load_prim(A.prims, best.slot);
+        const V hp = hit_point(ray, best.t);
+        const V hn = shape_normal(g, hp);
+        const Mat m = load_mat(mat, A.prim_shape[best.slot]);
+        alive = shade_bounce_pc(kp, ray, hp, hn, m, soft_term(L, S, hp, hn, ray.d, m, blocked), acc, att, 1e-3f);
+    }
+}
+
+// k_lights with the SoftSet: one wave per block, the lane stacks in LDS. FRAME = false: the
+// list, every walk per lane. FRAME = true: tile blockIdx.x in row-major tile order, camera rays
+// and all their sample rays as wave64 packets -- the K packets of a light converge on one small
+// disc -- later bounces per lane. No cost order, no split tiles, no compaction: launch_soft.
+template <bool MT, bool DISP, bool FRAME, bool PACK>
+__global__ __launch_bounds__(kBlock) RT_ACCEL_ATTR void k_soft(AccelPtrs A, const float4* __restrict__ mat, ShadeArgs q,
+                                                                LightSet L, SoftSet S, KParams kp) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    unsigned short* stt =
+        reinterpret_cast<unsigned short*>(lds_stack + static_cast<size_t>(kp.lane_stack) * blockDim.x) + threadIdx.x;
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;  // the list's ray
+    const int tile = static_cast<int>(blockIdx.x);             // the frame's tile
+    bool alive;
+    Ray ray{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 1.f)};
+    if constexpr (FRAME) {
+        const PixelCoord pc = tile_pixel(kp, tile);
+        ray = primary_ray(kp, pc.x, pc.y);
+        alive = pc.active;
+    } else {
+        alive = i < static_cast<unsigned>(q.n);
+        if (alive) {
+            const float4 a = q.rays[2 * static_cast<size_t>(i)], b = q.rays[2 * static_cast<size_t>(i) + 1];
+            ray = Ray{mk(a.x, a.y, a.z), mk(b.x, b.y, b.z)};
+        }
+    }
+    const bool have = alive;
+    V acc = mk(0.f, 0.f, 0.f), att = mk(1.f, 1.f, 1.f);
+    if (FRAME && kp.root_ok) {
+        // accel_tile's root test: a camera ray that misses the root's box takes the background
+        V rlo = mk(kp.root_lo[0], kp.root_lo[1], kp.root_lo[2]), rhi = mk(kp.root_hi[0], kp.root_hi[1], kp.root_hi[2]);
+        if (kp.root_ok == 2) {
+            const float4 a = A.anodes[4 * static_cast<size_t>(A.N - 1)], b = A.anodes[4 * static_cast<size_t>(A.N - 1) + 1];
+            rlo = mk(a.x, a.y, a.z);
+            rhi = mk(b.x, b.y, b.z);
+        }
+        if (alive && !ray_aabb(ray.o, inv_dir(ray.d), rlo, rhi)) {
+            acc = background(kp, tile_pixel(kp, tile).y);
+            alive = false;
+        }
+    }
+    WalkCount wc{0u, 0u, 0u, 0u};
+    // PACK: kSoftSlot dwords per lane after the lane stacks (launch_soft's LDS size)
+    float* pk = reinterpret_cast<float*>(lds_stack) + (static_cast<size_t>(kp.lane_stack) * blockDim.x * 6) / 4;
+    for (int depth = 0; depth < kp.maxBounces; ++depth) {
+        if (__ballot(alive) == 0) break;
+        if constexpr (FRAME)
+            bounce_step_soft<MT, PACK>(A, mat, kp, L, S, depth, ray, alive, acc, att,
+                                       [&]() { return tile_pixel(kp, tile).y; }, stk, stt, kp.lane_stack, wc, 1, 1, pk);
+        else
+            bounce_step_soft<MT, PACK>(A, mat, kp, L, S, depth, ray, alive, acc, att,
+                                       [&]() { return q.rays[2 * static_cast<size_t>(i)].w; }, stk, stt,
+                                       kp.lane_stack, wc, 0, 0, pk);
+    }
+    if (!have) return;
+    const float4 px = make_float4(acc.x, acc.y, acc.z, 1.0f);
+    if constexpr (FRAME) {
+        const PixelCoord pc = tile_pixel(kp, tile);
+        store_px<DISP ? kStoreDisplay : kStoreFloat>(kp, pc.r, pc.x, px);
+    } else {
+        store_px<DISP ? kStoreDisplay : kStoreFloat>(kp, shade_row(i), shade_col(i), px);
+    }
+}
+
+// k_lights_ref with the sample loop: the literal per-lane loop on both useBVH branches
+// (RT_KERNEL_LANE / RT_KERNEL_PACKET, contexts without a usable accelerator, far cameras).
+template <bool DISP, bool FRAME>
+__global__ __launch_bounds__(kBlock) void k_soft_ref(ShadeArgs q, LightSet L, SoftSet S, KParams kp) {
+    extern __shared__ int lds_stack[];
+    int* stk = lds_stack + threadIdx.x;
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    int r, x;  // the output pixel
+    V bg;
+    Ray ray;
+    if constexpr (FRAME) {
+        const PixelCoord pc = pixel_of(kp);
+        if (!pc.active) return;
+        r = pc.r;
+        x = pc.x;
+        bg = background(kp, pc.y);
+        ray = primary_ray(kp, pc.x, pc.y);
+    } else {
+        if (i >= static_cast<unsigned>(q.n)) return;
+        const float4 ra = q.rays[2 * static_cast<size_t>(i)], rb = q.rays[2 * static_cast<size_t>(i) + 1];
+        r = shade_row(i);
+        x = shade_col(i);
+        bg = background(kp, ra.w);
+        ray = Ray{mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z)};
+    }
+    V acc = mk(0.f, 0.f, 0.f), att = mk(1.f, 1.f, 1.f);
+    Counters c;
+    const float shadow_off = kp.useBVH ? 1e-3f : 1e-5f;  // :469 vs :565
+    for (int depth = 0; depth < kp.maxBounces; ++depth) {
+        const LaneHit hit = kp.useBVH ? lane_closest_bvh<false>(kp, kp.nodes, kp.geo_leaf, ray, stk, c)
+                                      : lane_closest_brute<false>(kp, kp.geo_lin, ray, c);
+        if (!hit.found) {
+            acc = acc + mulv(att, bg);
+            break;
+        }
+        const GeoRec g = load_rec(kp.useBVH ? kp.geo_leaf : kp.geo_lin, hit.slot);
+        const V hn = shape_normal(g, hit.p);
+        const Mat m = load_mat(kp.mat, g.idx);
+        unsigned long long blocked = 0;
+#pragma unroll 1
+        for (int l = 0; l < L.count; ++l) {
+            const int rays = soft_rays(S, l);
+#pragma unroll 1
+            for (int k = 0; k < rays; ++k) {
+                float ld;
+                const Ray sr = soft_ray(L, S, l, k, hit.p, hn, shadow_off, ld);
+                bool shadow;
+                if (kp.useBVH) {
+                    const LaneHit sh = lane_closest_bvh<false>(kp, kp.nodes, kp.geo_leaf, sr, stk, c);
+                    shadow = sh.found && sh.d < ld;
+                } else {
+                    shadow = lane_shadow_brute<false>(kp, kp.geo_lin, sr, ld, c);
+                }
+                if (shadow) blocked += 1ull << (7 * l);
+            }
+        }
+        if (!shade_bounce_pc(kp, ray, hit.p, hn, m, soft_term(L, S, hit.p, hn, ray.d, m, blocked), acc, att, 1e-3f))
+            break;
+    }
+    store_px<DISP ? kStoreDisplay : kStoreFloat>(kp, r, x, make_float4(acc.x, acc.y, acc.z, 1.0f));
+}
+
 // The general path of rt_set_samples: the sample frame was rendered by any kernel into a
 // scratch surface (compact rows, RGBA32F); one thread per output pixel applies the box
 // filter in the order rt_api.h fixes -- log2 N pairwise rounds along x, then along y,
@@ -3811,6 +4100,10 @@ struct rt_ctx {
     FlatLight light{};                       // light 0: the one light of every existing kernel
     FlatLight lights[RT_MAX_LIGHTS]{};       // rt_set_lights: the whole set (lights[0] == light)
     int nlights = 1;                         // its size; >= 2: the k_lights kernels (rtp::lights_route)
+    float soft_radii[RT_MAX_LIGHTS]{};       // rt_set_soft_shadows: light i's radius (0 from soft_count on)
+    int soft_count = 0;                      // 0: off; a radius > 0 below nlights: the k_soft kernels
+    int soft_samples = 0;                    // K (rtp::soft_route)
+    int soft_form = 0;  // rt_debug_soft: 0 = the default form of later bounces' samples, 1 = repacked, 2 = per lane
     rt_params params{0.f, 0.f, 0, 0, 0, 0};  // the reference's first frame sees zeros
     bool have_params = false;                // rt_set_params was called (rt_trace_pixels needs resX / resY)
     // rt_trace_rays_host / rt_trace_pixels: staging for the rays (or pixels) and the hits,
@@ -4931,6 +5224,10 @@ void inherit(rt_ctx* b, const rt_ctx* c) {
     b->light = c->light;
     std::copy(c->lights, c->lights + RT_MAX_LIGHTS, b->lights);
     b->nlights = c->nlights;
+    std::copy(c->soft_radii, c->soft_radii + RT_MAX_LIGHTS, b->soft_radii);
+    b->soft_count = c->soft_count;
+    b->soft_samples = c->soft_samples;
+    b->soft_form = c->soft_form;
     b->have_cam = b->have_light = true;
     b->params = c->params;
     b->kernel = RT_KERNEL_ACCEL;
@@ -5400,6 +5697,18 @@ int launch_accel(rt_ctx* c, const KParams& kin, const KParams& kout, const KPara
 // context's accelerator, one wave per 8x8 tile in row-major order, or k_lights_ref on k_lane's
 // grid. The set is the context's (a sub-context inherits its parent's). No cost order, no
 // latency mode, no compaction, no walk policy: the frame's walks are fixed (k_lights).
+// The frame of k_lights / k_soft: one wave per 8x8 tile in row-major tile order, the root's
+// bounds for the sky skip, the lane stacks.
+KParams tile_frame(rt_ctx* c, const KParams& kp) {
+    KParams k2 = kp;
+    k2.tiles_x = (kp.width + 7) / 8;
+    k2.tiles = k2.tiles_x * ((kp.out_rows + 7) / 8);
+    k2.root_ok = 0;  // (not with maxBounces = 0: launch_accel)
+    if (kp.maxBounces > 0 && kp.useBVH) root_bounds(c, k2);
+    k2.lane_stack = lane_stack_entries(c);
+    return k2;
+}
+
 void launch_lights(rt_ctx* c, const KParams& kp, bool accel, dim3 lane_grid) {
     const LightSet L = make_light_set(c->lights, c->nlights);
     const ShadeArgs q{nullptr, 0};
@@ -5409,15 +5718,46 @@ void launch_lights(rt_ctx* c, const KParams& kp, bool accel, dim3 lane_grid) {
         hipLaunchKernelGGL(kfn, lane_grid, dim3(kBlock), ref_stack_lds(kp), c->stream, q, L, kp);
         return;
     }
-    KParams k2 = kp;
-    k2.tiles_x = (kp.width + 7) / 8;
-    k2.tiles = k2.tiles_x * ((kp.out_rows + 7) / 8);
-    k2.root_ok = 0;  // (not with maxBounces = 0: launch_accel)
-    if (kp.maxBounces > 0 && kp.useBVH) root_bounds(c, k2);
-    k2.lane_stack = lane_stack_entries(c);
+    const KParams k2 = tile_frame(c, kp);
     auto kfn = c->accel.mt ? (disp ? k_lights<true, true, true> : k_lights<true, false, true>)
                            : (disp ? k_lights<false, true, true> : k_lights<false, false, true>);
     hipLaunchKernelGGL(kfn, dim3(k2.tiles), dim3(64), lane_stack_lds(k2), c->stream, accel_ptrs(c), c->mat, q, L, k2);
+}
+
+// Later bounces' sample rays repacked over the wave (k_soft's PACK) or per live lane:
+// rtp::soft_repack, the measured rule; rt_debug_soft overrides it.
+bool soft_pack(const rt_ctx* c, const KParams& kp) { return rtp::soft_repack(c->soft_form, kp.maxBounces); }
+size_t soft_lds(const KParams& kp, bool pack) {
+    return lane_stack_lds(kp) + (pack ? kSoftSlot * 64 * sizeof(int) : 0);
+}
+using SoftKernel = void (*)(AccelPtrs, const float4*, ShadeArgs, LightSet, SoftSet, KParams);
+template <bool FRAME, bool PACK>
+SoftKernel soft_kernel_of(bool mt, bool disp) {
+    return mt ? (disp ? k_soft<true, true, FRAME, PACK> : k_soft<true, false, FRAME, PACK>)
+              : (disp ? k_soft<false, true, FRAME, PACK> : k_soft<false, false, FRAME, PACK>);
+}
+template <bool FRAME>
+SoftKernel soft_kernel(bool mt, bool disp, bool pack) {
+    return pack ? soft_kernel_of<FRAME, true>(mt, disp) : soft_kernel_of<FRAME, false>(mt, disp);
+}
+
+// launch()'s render of a soft frame (rtp::soft_route): launch_lights with the context's radii
+// and K -- k_soft over the accelerator, one wave per 8x8 tile in row-major order, or k_soft_ref
+// on k_lane's grid.
+void launch_soft(rt_ctx* c, const KParams& kp, bool accel, dim3 lane_grid) {
+    const LightSet L = make_light_set(c->lights, c->nlights);
+    const SoftSet S = make_soft_set(c->soft_radii, c->soft_count, c->soft_samples);
+    const ShadeArgs q{nullptr, 0};
+    const bool disp = kp.rgb >= RT_FORMAT_RGBA8;
+    if (!accel) {
+        auto kfn = disp ? k_soft_ref<true, true> : k_soft_ref<false, true>;
+        hipLaunchKernelGGL(kfn, lane_grid, dim3(kBlock), ref_stack_lds(kp), c->stream, q, L, S, kp);
+        return;
+    }
+    const KParams k2 = tile_frame(c, kp);
+    const bool pack = soft_pack(c, k2);
+    hipLaunchKernelGGL(soft_kernel<true>(c->accel.mt, disp, pack), dim3(k2.tiles), dim3(64), soft_lds(k2, pack), c->stream,
+                       accel_ptrs(c), c->mat, q, L, S, k2);
 }
 
 int launch(rt_ctx* c, const KParams& kin, bool stats) {
@@ -5434,8 +5774,11 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
     // rt_set_lights: two or more lights render in k_lights / k_lights_ref; one light takes
     // every path below as it always did
     const rtp::LightsRoute lr = rtp::lights_route(c->nlights, stats, kind == RT_KERNEL_ACCEL);
+    // rt_set_soft_shadows: a light of the set with a radius > 0 renders in k_soft / k_soft_ref,
+    // one light included; consulted first, and off for every frame without such a light
+    const rtp::SoftRoute so = rtp::soft_route(c->nlights, c->soft_radii, stats, kind == RT_KERNEL_ACCEL);
     const rtp::Samples sp =
-        rtp::samples_plan(stats, kin.ss, rtp::accel_renders(kind == RT_KERNEL_ACCEL, lr), c->tile_times != nullptr,
+        rtp::samples_plan(stats, kin.ss, rtp::accel_renders(kind == RT_KERNEL_ACCEL, lr, so), c->tile_times != nullptr,
                           c->ss_general, c->adaptive >= 0.0f, c->convert_pass, kin.rgb >= RT_FORMAT_RGBA8);
     KParams kout = kin;  // adaptive: the one-sample output frame, B's, with the dispatch's dst / pitch / format
     if (sp.adaptive) {
@@ -5478,6 +5821,10 @@ int launch(rt_ctx* c, const KParams& kin, bool stats) {
     if (stats) {
         hipLaunchKernelGGL(k_lane<true>, grid, dim3(kBlock), lds, c->stream, c->geo_leaf, c->geo_lin, c->mat,
                            c->nodes, kp);
+    } else if (so != rtp::kSoftOff) {
+        launch_soft(c, kp, so == rtp::kSoftAccel, grid);
+        if (sp.filter) launch_box_filter(c, kin);
+        kind = so == rtp::kSoftAccel ? RT_KERNEL_SOFT : RT_KERNEL_LANE;
     } else if (lr != rtp::kLightsOff) {
         launch_lights(c, kp, lr == rtp::kLightsAccel, grid);
         if (sp.filter) launch_box_filter(c, kin);
@@ -5808,15 +6155,25 @@ int shade_launch(rt_ctx* c, const float4* rays, int n, void* pixels, int format)
     // rt_set_lights: two or more lights (this context's set) in k_lights' list form, over the
     // same target; one light takes k_shade / k_shade_ref as it always did
     const rtp::LightsRoute lr = rtp::lights_route(c->nlights, false, accel);
-    if (lr == rtp::kLightsAccel) {
+    // rt_set_soft_shadows: a radius > 0 in the set takes k_soft's list form, consulted first
+    const rtp::SoftRoute so = rtp::soft_route(c->nlights, c->soft_radii, false, accel);
+    const LightSet L = make_light_set(c->lights, c->nlights);
+    const SoftSet S = make_soft_set(c->soft_radii, c->soft_count, c->soft_samples);
+    const dim3 waves((static_cast<unsigned>(n) + 63u) / 64u), blocks((static_cast<unsigned>(n) + kBlock - 1u) / kBlock);
+    if (so == rtp::kSoftAccel) {
+        const bool pack = soft_pack(c, kp);
+        hipLaunchKernelGGL(soft_kernel<false>(mt, disp, pack), waves, dim3(64), soft_lds(kp, pack), c->stream,
+                           accel_ptrs(t), t->mat, q, L, S, kp);
+    } else if (so == rtp::kSoftRef) {
+        auto kfn = disp ? k_soft_ref<true, false> : k_soft_ref<false, false>;
+        hipLaunchKernelGGL(kfn, blocks, dim3(kBlock), ref_stack_lds(kp), c->stream, q, L, S, kp);
+    } else if (lr == rtp::kLightsAccel) {
         auto kfn = mt ? (disp ? k_lights<true, true, false> : k_lights<true, false, false>)
                       : (disp ? k_lights<false, true, false> : k_lights<false, false, false>);
-        hipLaunchKernelGGL(kfn, dim3((static_cast<unsigned>(n) + 63u) / 64u), dim3(64), lane_stack_lds(kp), c->stream,
-                           accel_ptrs(t), t->mat, q, make_light_set(c->lights, c->nlights), kp);
+        hipLaunchKernelGGL(kfn, waves, dim3(64), lane_stack_lds(kp), c->stream, accel_ptrs(t), t->mat, q, L, kp);
     } else if (lr == rtp::kLightsRef) {
         auto kfn = disp ? k_lights_ref<true, false> : k_lights_ref<false, false>;
-        hipLaunchKernelGGL(kfn, dim3((static_cast<unsigned>(n) + kBlock - 1u) / kBlock), dim3(kBlock), ref_stack_lds(kp),
-                           c->stream, q, make_light_set(c->lights, c->nlights), kp);
+        hipLaunchKernelGGL(kfn, blocks, dim3(kBlock), ref_stack_lds(kp), c->stream, q, L, kp);
     } else if (accel) {
         const bool split = !mt && (c->shade_split ? c->shade_split == 2 : t->accel.st.item_ref.size() >= kShadeSplitItems);
         auto kfn = mt      ? (disp ? k_shade<true, false, true> : k_shade<true, false, false>)
@@ -6365,6 +6722,28 @@ int rt_get_lights(rt_ctx* c, FlatLight* lights, int cap, int* count) {
     if (lights)
         for (int i = 0; i < std::min(cap, n); ++i) lights[i] = c->lights[i];
     if (count) *count = n;
+    return RT_OK;
+}
+
+int rt_set_soft_shadows(rt_ctx* c, const float* radii, int count, int samples) {
+    if (!c || count < 0 || count > RT_MAX_LIGHTS) return RT_ERR_INVALID;
+    if (count > 0) {
+        if (!radii || samples < 1 || samples > RT_MAX_SHADOW_SAMPLES) return RT_ERR_INVALID;
+        for (int i = 0; i < count; ++i)
+            if (!std::isfinite(radii[i]) || radii[i] < 0.0f) return RT_ERR_INVALID;
+    }
+    for (int i = 0; i < RT_MAX_LIGHTS; ++i) c->soft_radii[i] = i < count ? radii[i] : 0.0f;
+    c->soft_count = count;
+    c->soft_samples = count > 0 ? samples : 0;
+    return RT_OK;
+}
+
+int rt_get_soft_shadows(rt_ctx* c, float* radii, int cap, int* count, int* samples) {
+    if (!c || (radii && cap < 0)) return RT_ERR_INVALID;
+    if (radii)
+        for (int i = 0; i < std::min(cap, c->soft_count); ++i) radii[i] = c->soft_radii[i];
+    if (count) *count = c->soft_count;
+    if (samples) *samples = c->soft_samples;
     return RT_OK;
 }
 
@@ -7040,6 +7419,14 @@ extern "C" int rt_debug_ao(rt_ctx* c, int form, int waves) {
     if (!c || form < 0 || form > 2 || (waves != 0 && waves != 1 && waves != 2 && waves != 4)) return RT_ERR_INVALID;
     c->ao_form = form;
     c->ao_waves = waves;
+    return RT_OK;
+}
+
+// Diagnostics (tools/bench_soft.py): k_soft walks the sample rays of bounces >= 1 repacked
+// over the wave (form 1) or per live lane (form 2; 0 = the default form). Same pixels either way.
+extern "C" int rt_debug_soft(rt_ctx* c, int form) {
+    if (!c || form < 0 || form > 2) return RT_ERR_INVALID;
+    c->soft_form = form;
     return RT_OK;
 }
 

@@ -98,6 +98,8 @@ TRACE_CLOSEST, TRACE_ANY = 0, 1
 KERNEL_AUTO, KERNEL_LANE, KERNEL_PACKET, KERNEL_ACCEL = 0, 1, 2, 3
 KERNEL_LIGHTS = 4  # reported by accel_info()["last_kernel"] only: a frame of two or more lights (set_lights)
 MAX_LIGHTS = 8     # RT_MAX_LIGHTS
+KERNEL_SOFT = 5    # reported by accel_info()["last_kernel"] only: a frame of area lights (set_soft_shadows)
+MAX_SHADOW_SAMPLES = 64  # RT_MAX_SHADOW_SAMPLES
 SCHED_ROWS, SCHED_COST, SCHED_COST_XCD = 0, 1, 2
 TREE_REFERENCE, TREE_SCENE = 0, 1
 
@@ -252,6 +254,7 @@ RT_SYMBOLS = {
     "rt_read_nodes": (_I, [_P, _P, _I]),
     "rt_set_camera": (_I, [_P, _P]), "rt_set_light": (_I, [_P, _P]),
     "rt_set_lights": (_I, [_P, _P, _I]), "rt_get_lights": (_I, [_P, _P, _I, _P]),
+    "rt_set_soft_shadows": (_I, [_P, _P, _I, _I]), "rt_get_soft_shadows": (_I, [_P, _P, _I, _P, _P]),
     "rt_set_params": (_I, [_P, _P]), "rt_set_kernel": (_I, [_P, _I]),
     "rt_dispatch": (_I, [_P, _I, _I, _I, _I]),
     "rt_dispatch_rows": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t]),
@@ -724,6 +727,21 @@ class ComputeShader:
         self._chk(self._lib.rt_get_lights(self._h, _ptr(out), MAX_LIGHTS, C.byref(n)), "rt_get_lights")
         return out[:n.value]
 
+    def set_soft_shadows(self, radii, samples=16):
+        """rt_set_soft_shadows: light i of the set in force gets the radius radii[i] (lights past
+        the list stay points) and every light with a radius > 0 `samples` shadow rays, from the
+        next dispatch on; None or an empty list turns soft shadows off."""
+        radii = np.zeros(0, np.float32) if radii is None else np.ascontiguousarray(radii, np.float32).reshape(-1)
+        self._chk(self._lib.rt_set_soft_shadows(self._h, _ptr(radii), len(radii), int(samples)), "rt_set_soft_shadows")
+
+    def get_soft_shadows(self):
+        """rt_get_soft_shadows: (radii as float32, samples); (empty, 0) while soft shadows are off."""
+        out = np.zeros(MAX_LIGHTS, np.float32)
+        n, k = C.c_int(), C.c_int()
+        self._chk(self._lib.rt_get_soft_shadows(self._h, _ptr(out), MAX_LIGHTS, C.byref(n), C.byref(k)),
+                  "rt_get_soft_shadows")
+        return out[:n.value], k.value
+
     def set_params(self, resX, resY, maxBounces=3, useBVH=True, useFresnel=False, useMollerTrumbore=False):
         p = rt_params(float(resX), float(resY), int(maxBounces), int(bool(useBVH)), int(bool(useFresnel)),
                       int(bool(useMollerTrumbore)))
@@ -1041,6 +1059,14 @@ class ComputeShader:
         fn.argtypes = [_P, _I, _I]
         fn.restype = _I
         self._chk(fn(self._h, int(form), int(waves)), "rt_debug_ao")
+
+    def debug_soft(self, form=0):
+        """Diagnostics: the soft-shadow kernel walks the sample rays of bounces >= 1 repacked over
+        the wave (form 1) or per live lane (form 2; 0: the default form). Same pixels either way."""
+        fn = self._lib.rt_debug_soft
+        fn.argtypes = [_P, _I]
+        fn.restype = _I
+        self._chk(fn(self._h, int(form)), "rt_debug_soft")
 
     def debug_ss_general(self, on):
         """Diagnostics: supersampled frames render the sample frame and filter it with a second
